@@ -2,6 +2,8 @@
 """Headline benchmark: SART iterations/s and GFLOPS on a dense synthetic RTM (BASELINE.json).
 
     python bench.py [--gpus N --steps K --warmup W]           # N ranks (self-launched when N > 1)
+    python bench.py --full [...]                              # ... plus the untimed self-check
+    python bench.py --dump-outputs DIR [...]                  # ... and the last timed step's results as DIR/*.npy
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
 One *step* = one frame solve with a cold start and exactly ``--iters`` SART iterations (100 by
@@ -16,8 +18,13 @@ Launching: ``--gpus N`` with N > 1 and no launcher environment (WORLD_SIZE / MPI
 line and exit code through, like the reference's ``mpirun -np N`` (reference main.cpp:63-68). Under a
 launcher, a world size different from ``--gpus`` is an error (exit 1). A per-rank watchdog exits non-zero
 when a stage (setup, self-check, warmup, timed steps) makes no progress for ``--watchdog`` seconds.
-Before timing, a one-iteration self-check compares the fused sweep and the two-pass kernels on the same shard
-with the device fp64 oracle (``selfcheck`` in the JSON line).
+
+A plain run does only what the headline figure needs: set-up, ``--warmup`` untimed steps, ``--steps`` timed steps,
+the JSON line (``ms_per_step`` is the wall time of one timed step). ``--full`` adds, before timing, a one-iteration
+self-check that compares the fused sweep and the two-pass kernels on the same shard with the device fp64 oracle
+(``selfcheck`` in the JSON line, null without ``--full``). ``--dump-outputs DIR`` writes what the last timed step
+returned (solution, convergence, iterations) as ``DIR/<name>.npy``; the inputs depend only on the arguments
+(``--seed``), so two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -168,6 +175,30 @@ def _split_a_dtype(solver) -> str:
             + (bwd % "column" if "%s" in bwd else bwd) + "; fp32 accumulation")
 
 
+DUMP_BYTES = 32 << 20  # per array written by --dump-outputs
+
+
+def dump_outputs(directory: str, frames: list, iterations: list, rank: int, all_ranks: bool) -> None:
+    """What the last timed step returned to its caller, as float64 ``.npy`` files: ``solution`` [frames, voxels]
+    (the frames of the step in order), ``convergence`` and ``iterations`` [frames]. A solution above DUMP_BYTES keeps
+    a fixed sample of its voxels (seeded, the same columns for every frame and every run of the same shape). Row
+    shards return the whole solution on every rank, so rank 0 writes; column shards (``all_ranks``) return their
+    block of voxels, written per rank as ``<name>_rank<r>.npy``."""
+    import numpy as np
+
+    if rank != 0 and not all_ranks:
+        return
+    x = np.stack([np.asarray(r.solution, dtype=np.float64).ravel() for r in frames])
+    keep = DUMP_BYTES // (8 * x.shape[0])
+    if x.shape[1] > keep:
+        x = x[:, np.sort(np.random.default_rng(20240229).choice(x.shape[1], size=keep, replace=False))]
+    tag = f"_rank{rank}" if all_ranks and rank else ""
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, f"solution{tag}.npy"), np.ascontiguousarray(x))
+    np.save(os.path.join(directory, f"convergence{tag}.npy"), np.array([r.convergence for r in frames], np.float64))
+    np.save(os.path.join(directory, f"iterations{tag}.npy"), np.array(iterations, np.float64))
+
+
 def main() -> int:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--gpus", type=int, default=1, help="ranks (one per GPU); > 1 self-launches under torchrun")
@@ -176,7 +207,13 @@ def main() -> int:
                          "collectives, two-pass kernels)")
     ap.add_argument("--watchdog", type=float, default=600.0,
                     help="seconds without progress after which a rank exits non-zero (0: off)")
-    ap.add_argument("--no-selfcheck", action="store_true", help="skip the untimed fused-vs-two-pass check")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the untimed fused-vs-two-pass self-check "
+                         "against the device fp64 oracle (off by default: a plain run sets up, warms up and times)")
+    ap.add_argument("--no-selfcheck", action="store_true", help="with --full: skip the untimed fused-vs-two-pass check")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float64): "
+                         "solution, convergence, iterations; a fixed seeded sample of voxels when larger than 32 MB")
     ap.add_argument("--launch-check", action="store_true",
                     help="launch and rendezvous only (no GPU work): prints the JSON line with value null")
     ap.add_argument("--steps", type=int, default=5)
@@ -222,6 +259,8 @@ def main() -> int:
 
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     world = launched_world()
     if world is None and args.gpus > 1:
         env_extra = {}
@@ -308,9 +347,10 @@ def main() -> int:
                 self.s = s
 
             def solve(self, gb):
-                rs = self.s.solve_batch(gb)
+                rs = self.last = self.s.solve_batch(gb)
                 r = rs[-1]
-                r.iterations = sum(x.iterations for x in rs)
+                self.iterations = [x.iterations for x in rs]  # per frame (--dump-outputs)
+                r.iterations = sum(self.iterations)
                 return r
 
         runner = _Batch(solver)
@@ -339,7 +379,7 @@ def main() -> int:
 
     counts = _Counts()
     selfcheck = None
-    if not multi and solver.use_fused and not args.no_selfcheck:
+    if args.full and not multi and solver.use_fused and not args.no_selfcheck:
         # Untimed: ONE iteration from the cold start (x1 = x0 + d(x0): every part of the sweep runs once) with
         # the fused sweep and with the two-pass kernels on this very shard and grid, both against the device fp64
         # oracle (models/oracle.py, all ranks). At x0 the residual is large, so the comparison measures the
@@ -398,6 +438,10 @@ def main() -> int:
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     elapsed = comm.all_reduce_scalar(elapsed, op="max")
+    if args.dump_outputs:
+        frames = runner.last if multi else [res]
+        dump_outputs(args.dump_outputs, frames, runner.iterations if multi else [res.iterations], comm.rank,
+                     all_ranks=cols)
 
     iters_per_s = iters / elapsed
     flop_per_iter = 4.0 * npix_total * nvox_total
@@ -432,7 +476,7 @@ def main() -> int:
         "fused_schedule": solver.k.fused_last_schedule() if use_fused else None,
         "fused_grid": ({"J": solver.geom.J, "I": solver.geom.I, "workgroups": solver.geom.grid,
                         "ld": solver.ld, "kw": solver.geom.kw, "xcd_local": solver.geom.xl} if use_fused else None),
-        "selfcheck": selfcheck,
+        "selfcheck": selfcheck,  # --full only
         "shared_gpus": bool(getattr(solver, "shared_device", False)) if not multi else None,
         "fused_plan_cus": solver.plan_cus if use_fused else None,
         "startup": startup,

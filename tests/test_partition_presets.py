@@ -50,6 +50,37 @@ def test_bench_presets_match_baseline_configs():
     assert two["npix"] * two["nvox"] * 4 < 288e9 * 0.95  # shard + workspaces fit one GPU
 
 
+def test_bench_dump_outputs_writes_float64_and_samples_large_solutions(tmp_path):
+    import types
+
+    import numpy as np
+
+    b = _bench()
+    rng = np.random.default_rng(0)
+    frames = [types.SimpleNamespace(solution=rng.random(1000), convergence=0.5 + f) for f in range(3)]
+    b.dump_outputs(str(tmp_path / "a"), frames, [7, 8, 9], rank=0, all_ranks=False)
+    x = np.load(tmp_path / "a" / "solution.npy")
+    assert x.dtype == np.float64 and x.shape == (3, 1000)  # below the cap: everything, frames in order
+    assert all(np.array_equal(x[f], frames[f].solution) for f in range(3))
+    assert np.load(tmp_path / "a" / "convergence.npy").tolist() == [0.5, 1.5, 2.5]
+    assert np.load(tmp_path / "a" / "iterations.npy").tolist() == [7.0, 8.0, 9.0]
+    # above the cap: the same sorted sample of voxels for every frame and every call
+    b.DUMP_BYTES = 3 * 8 * 100
+    for d in ("b", "c"):
+        b.dump_outputs(str(tmp_path / d), frames, [7, 8, 9], rank=0, all_ranks=False)
+    y = np.load(tmp_path / "b" / "solution.npy")
+    assert y.shape == (3, 100) and y.nbytes <= b.DUMP_BYTES
+    assert np.array_equal(y, np.load(tmp_path / "c" / "solution.npy"))
+    cols = [int(np.flatnonzero(frames[0].solution == v)[0]) for v in y[0]]
+    assert cols == sorted(set(cols)) and np.array_equal(y[2], frames[2].solution[cols])
+    # row shards: only rank 0 writes; column shards: every rank writes its block under its own name
+    b.dump_outputs(str(tmp_path / "d"), frames, [7, 8, 9], rank=1, all_ranks=False)
+    assert not (tmp_path / "d").exists()
+    b.dump_outputs(str(tmp_path / "d"), frames, [7, 8, 9], rank=1, all_ranks=True)
+    assert sorted(p.name for p in (tmp_path / "d").iterdir()) == [
+        "convergence_rank1.npy", "iterations_rank1.npy", "solution_rank1.npy"]
+
+
 @pytest.mark.parametrize("n", [4096, 65536, 262144, 1000, 17])
 def test_grid_dims_factorise(n):
     nx, ny, nz = _bench().grid_dims(n)

@@ -652,7 +652,7 @@ for step in "$@"; do
     r4bf16cw)  # wide bf16 tiles, XCD-local vs chip-wide groups, self-check on (rc 1 = self-check failed: keep going)
       for spec in "131072:1:" "131072:0:" "150000:0:4" "150000:0:2" "163840:0:" "150000:1:"; do
         IFS=: read -r v xl t <<< "$spec"
-        SART_BF16_XL=$xl SART_BF16_T=$t run bf16cw_${v}_${xl}_${t} 200 python bench.py --steps 3 --warmup 1 --iters 50 --nvox $v --npix 32768 --rtm-dtype bf16 || exit 1
+        SART_BF16_XL=$xl SART_BF16_T=$t run bf16cw_${v}_${xl}_${t} 200 python bench.py --full --steps 3 --warmup 1 --iters 50 --nvox $v --npix 32768 --rtm-dtype bf16 || exit 1
         grep -h '^{' "$OUT/bf16cw_${v}_${xl}_${t}.log" >> "$OUT/bf16cw.jsonl" || true
         grep -h "self-check" "$OUT/bf16cw_${v}_${xl}_${t}.log" | tail -1 || true
       done ;;
@@ -678,10 +678,10 @@ for step in "$@"; do
       done ;;
     r4bf16seg)  # chip-wide bf16 at 150000 voxels: does a shorter back-projection chain (segments) fix the self-check?
       for seg in 280 700; do
-        SART_BF16_XL=0 SART_BF16_T=4 SART_FUSED_SEG=$seg run bf16seg_$seg 200 python bench.py --steps 3 --warmup 1 --iters 50 --nvox 150000 --npix 32768 --rtm-dtype bf16 || true
+        SART_BF16_XL=0 SART_BF16_T=4 SART_FUSED_SEG=$seg run bf16seg_$seg 200 python bench.py --full --steps 3 --warmup 1 --iters 50 --nvox 150000 --npix 32768 --rtm-dtype bf16 || true
         grep -h "self-check\|^{" "$OUT/bf16seg_$seg.log" | cut -c1-300 | tail -2 || true
       done
-      SART_BF16_XL=1 run bf16seg_xl 200 python bench.py --steps 3 --warmup 1 --iters 50 --nvox 150000 --npix 32768 --rtm-dtype bf16 || true ;;
+      SART_BF16_XL=1 run bf16seg_xl 200 python bench.py --full --steps 3 --warmup 1 --iters 50 --nvox 150000 --npix 32768 --rtm-dtype bf16 || true ;;
     r4bf16test) run pytest_bf16 900 python -u -m pytest tests/test_gpu_bf16.py -m gpu -x -q -p no:cacheprovider --timeout 300 --timeout-method thread ;;
     r4pmcbwd)  # PMC of the split-A 64-frame back-projection (probe, default kernel): issue / co-execution counters
       PROBE_ABL=0 PROBE_BWD="lds:2" timeout -s KILL 120 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_VALU_MFMA_BUSY_CYCLES SQ_VALU_MFMA_COEXEC_CYCLES GRBM_GUI_ACTIVE \
