@@ -506,30 +506,90 @@ PYBIND11_MODULE(_sart_hip, m) {
                                  P<uint64_t>(gran), I, J, P<sart::SartState>(st), P<unsigned>(xcnt), S(stream));
     });
     m.def("fused_min_bytes_from_env", &sart::fused_min_bytes_from_env);
+    // The multi-frame MFMA projections: every direct kernel call plans from the environment as it is now
+    // (MfKnobs::from_env(); the engine plans once, in its constructor)
     m.def("mf_forward_num_splits", &sart::mf_forward_num_splits, py::arg("ld"), py::arg("nrows_pad"), py::arg("target") = 0);
     m.def("mf_backproject_num_splits", &sart::mf_backproject_num_splits);
     m.def("mf_set_depth", &sart::mf_set_depth);
     m.def("mf_set_rows", &sart::mf_set_rows);
     m.def("mf_set_vox", &sart::mf_set_vox);
-    m.def("mf_forward", [](uintptr_t A, int64_t ld, int64_t nrows, int64_t nrows_pad, uintptr_t X, int64_t ldx,
-                           uintptr_t Fout, int nsplit, uintptr_t stream, int nf) {
-        sart::launch_mf_forward(P<const float>(A), ld, nrows, nrows_pad, P<const float>(X), ldx, P<float>(Fout),
-                                nsplit, nf, S(stream));
-    }, py::arg("A"), py::arg("ld"), py::arg("nrows"), py::arg("nrows_pad"), py::arg("X"), py::arg("ldx"),
-       py::arg("Fout"), py::arg("nsplit"), py::arg("stream"), py::arg("nf") = 16);
     m.def("mf_backproject_b16_num_splits", &sart::mf_backproject_b16_num_splits, py::arg("ld"), py::arg("nrows"),
           py::arg("a32") = false);
     m.def("mf_backproject_b16_vox_align", &sart::mf_backproject_b16_vox_align, py::arg("ld"), py::arg("a32") = false);
-    m.def("mf_forward_x3", [](uintptr_t A, int64_t ld, int64_t nrows, int64_t nrows_pad, uintptr_t Xh, uintptr_t Xl,
-                              uintptr_t Fout, int nsplit, uintptr_t stream, int nf, bool xblk) {
-        sart::launch_mf_forward_x3(P<const float>(A), ld, nrows, nrows_pad, P<const sart::bf16_t>(Xh),
-                                   P<const sart::bf16_t>(Xl), P<float>(Fout), nsplit, nf, S(stream), xblk);
+    auto key_dict = [](const sart::MfKey& k) {
+        py::dict d;
+        d["path"] = sart::mf_path_name(k.path);
+        d["forward"] = k.forward;
+        d["ng"] = k.ng;
+        d["depth"] = k.depth;
+        d["tile"] = k.tile;
+        d["kb"] = k.kb;
+        d["lds"] = k.lds;
+        d["as"] = k.as;
+        d["early"] = k.early;
+        d["nt"] = k.nt;
+        d["mw"] = k.mw;
+        return d;
+    };
+    // path: "fp32", "b16", "x3" or "h16"; nsplit 0: the planner's split count (what the engine allocates for)
+    m.def("mf_plan_forward", [key_dict](const std::string& path, int nf, int64_t ld, int64_t nrows_pad, int nsplit) {
+        const sart::MfFwdPlan p = sart::mf_plan_forward(sart::mf_path_from_name(path), nf, ld, nrows_pad,
+                                                        sart::MfKnobs::from_env(), nsplit);
+        py::dict d = key_dict(p.key);
+        d["nsplit"] = p.nsplit;
+        d["cps"] = p.cps;
+        d["grid"] = py::make_tuple(p.grid_x, p.nsplit);
+        return d;
+    }, py::arg("path"), py::arg("nf"), py::arg("ld"), py::arg("nrows_pad"), py::arg("nsplit") = 0);
+    m.def("mf_plan_backproject", [key_dict](const std::string& path, int nf, int64_t ld, int64_t nrows, int nsplit) {
+        const sart::MfBwdPlan p = sart::mf_plan_backproject(sart::mf_path_from_name(path), nf, ld, nrows,
+                                                            sart::MfKnobs::from_env(), nsplit);
+        py::dict d = key_dict(p.key);
+        d["nsplit"] = p.nsplit;
+        d["rps"] = p.rps;
+        d["vox_align"] = p.vox_align;
+        d["grid"] = py::make_tuple(p.grid_x(0, ld), p.nsplit);
+        return d;
+    }, py::arg("path"), py::arg("nf"), py::arg("ld"), py::arg("nrows"), py::arg("nsplit") = 0);
+    // the variant table's keys of one path and direction, each with the knob setting ("env") that selects it
+    m.def("mf_variants", [key_dict](const std::string& path, int nf, bool forward) {
+        py::list out;
+        for (const sart::MfKey& k : sart::mf_variants(sart::mf_path_from_name(path), forward, nf)) {
+            py::dict d = key_dict(k), env;
+            for (const auto& kv : sart::mf_key_env(k)) env[py::str(kv.first)] = kv.second;
+            d["env"] = env;
+            out.append(d);
+        }
+        return out;
+    }, py::arg("path"), py::arg("nf"), py::arg("forward") = true);
+    auto fwd_plan = [](sart::MfPath path, int nf, int64_t ld, int64_t nrows_pad, int nsplit, const char* what) {
+        if (nsplit < 1) throw std::runtime_error(std::string(what) + ": nsplit must be >= 1");
+        return sart::mf_plan_forward(path, nf, ld, nrows_pad, sart::MfKnobs::from_env(), nsplit);
+    };
+    auto bwd_plan = [](sart::MfPath path, int nf, int64_t ld, int64_t nrows, int nsplit, const char* what) {
+        if (nsplit < 1) throw std::runtime_error(std::string(what) + ": nsplit must be >= 1");
+        return sart::mf_plan_backproject(path, nf, ld, nrows, sart::MfKnobs::from_env(), nsplit);
+    };
+    m.def("mf_forward", [fwd_plan](uintptr_t A, int64_t ld, int64_t nrows, int64_t nrows_pad, uintptr_t X, int64_t ldx,
+                                   uintptr_t Fout, int nsplit, uintptr_t stream, int nf) {
+        if (ldx != ld) throw std::runtime_error("mf_forward: ld must be a multiple of 64 and ldx == ld");
+        sart::launch_mf_forward(fwd_plan(sart::MfPath::fp32, nf, ld, nrows_pad, nsplit, "mf_forward"),
+                                P<const float>(A), nrows, P<const float>(X), P<float>(Fout), S(stream));
+    }, py::arg("A"), py::arg("ld"), py::arg("nrows"), py::arg("nrows_pad"), py::arg("X"), py::arg("ldx"),
+       py::arg("Fout"), py::arg("nsplit"), py::arg("stream"), py::arg("nf") = 16);
+    m.def("mf_forward_x3", [fwd_plan](uintptr_t A, int64_t ld, int64_t nrows, int64_t nrows_pad, uintptr_t Xh,
+                                      uintptr_t Xl, uintptr_t Fout, int nsplit, uintptr_t stream, int nf, bool xblk) {
+        sart::launch_mf_forward_x3(fwd_plan(sart::MfPath::x3, nf, ld, nrows_pad, nsplit, "mf_forward_x3"),
+                                   P<const float>(A), nrows, P<const sart::bf16_t>(Xh), P<const sart::bf16_t>(Xl),
+                                   P<float>(Fout), S(stream), xblk);
     }, py::arg("A"), py::arg("ld"), py::arg("nrows"), py::arg("nrows_pad"), py::arg("Xh"), py::arg("Xl"),
        py::arg("Fout"), py::arg("nsplit"), py::arg("stream"), py::arg("nf"), py::arg("xblk") = false);
-    m.def("mf_backproject_x3", [](uintptr_t A, int64_t ld, int64_t nrows, uintptr_t Wh, uintptr_t Wl, int64_t ldw,
-                                  int nsplit, uintptr_t partial, uintptr_t stream, int nf, int64_t v0, int64_t v1) {
-        sart::launch_mf_backproject_x3(P<const float>(A), ld, nrows, P<const sart::bf16_t>(Wh),
-                                       P<const sart::bf16_t>(Wl), ldw, nsplit, P<float>(partial), nf, S(stream), v0, v1);
+    m.def("mf_backproject_x3", [bwd_plan](uintptr_t A, int64_t ld, int64_t nrows, uintptr_t Wh, uintptr_t Wl,
+                                          int64_t ldw, int nsplit, uintptr_t partial, uintptr_t stream, int nf,
+                                          int64_t v0, int64_t v1) {
+        sart::launch_mf_backproject_x3(bwd_plan(sart::MfPath::x3, nf, ld, nrows, nsplit, "mf_backproject_x3"),
+                                       P<const float>(A), P<const sart::bf16_t>(Wh), P<const sart::bf16_t>(Wl), ldw,
+                                       P<float>(partial), S(stream), v0, v1);
     }, py::arg("A"), py::arg("ld"), py::arg("nrows"), py::arg("Wh"), py::arg("Wl"), py::arg("ldw"), py::arg("nsplit"),
        py::arg("partial"), py::arg("stream"), py::arg("nf") = 16, py::arg("v0") = 0, py::arg("v1") = -1);
     m.def("mf_split_x", [](uintptr_t X, int64_t n, uintptr_t hi, uintptr_t lo, uintptr_t stream, bool perm,
@@ -545,11 +605,12 @@ PYBIND11_MODULE(_sart_hip, m) {
     m.def("absmax_pow2_scale", [](uintptr_t A, int64_t n, uintptr_t scratch, uintptr_t stream) {
         return sart::absmax_pow2_scale(P<const float>(A), n, P<unsigned>(scratch), S(stream));
     });
-    m.def("mf_backproject_h16", [](uintptr_t A, int64_t ld, int64_t nrows, uintptr_t W1, uintptr_t W2, int64_t ldw,
-                                   int nsplit, uintptr_t partial, uintptr_t stream, int nf, int64_t v0, int64_t v1,
-                                   uintptr_t csc, uintptr_t inv_scale) {
-        sart::launch_mf_backproject_h16(P<const float>(A), ld, nrows, P<const uint16_t>(W1), P<const uint16_t>(W2), ldw,
-                                        nsplit, P<float>(partial), nf, S(stream), v0, v1, P<const float>(csc),
+    m.def("mf_backproject_h16", [bwd_plan](uintptr_t A, int64_t ld, int64_t nrows, uintptr_t W1, uintptr_t W2,
+                                           int64_t ldw, int nsplit, uintptr_t partial, uintptr_t stream, int nf,
+                                           int64_t v0, int64_t v1, uintptr_t csc, uintptr_t inv_scale) {
+        sart::launch_mf_backproject_h16(bwd_plan(sart::MfPath::h16, nf, ld, nrows, nsplit, "mf_backproject_h16"),
+                                        P<const float>(A), P<const uint16_t>(W1), P<const uint16_t>(W2), ldw,
+                                        P<float>(partial), S(stream), v0, v1, P<const float>(csc),
                                         P<const float>(inv_scale));
     }, py::arg("A"), py::arg("ld"), py::arg("nrows"), py::arg("W1"), py::arg("W2"), py::arg("ldw"), py::arg("nsplit"),
        py::arg("partial"), py::arg("stream"), py::arg("nf"), py::arg("v0"), py::arg("v1"), py::arg("csc"),
@@ -567,12 +628,12 @@ PYBIND11_MODULE(_sart_hip, m) {
                                   P<float>(xinv), S(stream), perm, blocked);
     }, py::arg("X"), py::arg("ld"), py::arg("nf"), py::arg("x1"), py::arg("x2"), py::arg("xmax"), py::arg("xinv"),
        py::arg("stream"), py::arg("perm") = true, py::arg("blocked") = false);
-    m.def("mf_forward_h16", [](uintptr_t A, int64_t ld, int64_t nrows, int64_t nrows_pad, uintptr_t X1, uintptr_t X2,
-                               uintptr_t Fout, int nsplit, uintptr_t stream, int nf, bool xblk, uintptr_t rsc,
-                               uintptr_t xinv) {
-        sart::launch_mf_forward_h16(P<const float>(A), ld, nrows, nrows_pad, P<const uint16_t>(X1),
-                                    P<const uint16_t>(X2), P<float>(Fout), nsplit, nf, S(stream), xblk,
-                                    P<const float>(rsc), P<const float>(xinv));
+    m.def("mf_forward_h16", [fwd_plan](uintptr_t A, int64_t ld, int64_t nrows, int64_t nrows_pad, uintptr_t X1,
+                                       uintptr_t X2, uintptr_t Fout, int nsplit, uintptr_t stream, int nf, bool xblk,
+                                       uintptr_t rsc, uintptr_t xinv) {
+        sart::launch_mf_forward_h16(fwd_plan(sart::MfPath::h16, nf, ld, nrows_pad, nsplit, "mf_forward_h16"),
+                                    P<const float>(A), nrows, P<const uint16_t>(X1), P<const uint16_t>(X2),
+                                    P<float>(Fout), S(stream), xblk, P<const float>(rsc), P<const float>(xinv));
     }, py::arg("A"), py::arg("ld"), py::arg("nrows"), py::arg("nrows_pad"), py::arg("X1"), py::arg("X2"),
        py::arg("Fout"), py::arg("nsplit"), py::arg("stream"), py::arg("nf"), py::arg("xblk"), py::arg("rsc"),
        py::arg("xinv"));
@@ -582,23 +643,25 @@ PYBIND11_MODULE(_sart_hip, m) {
                                 S(stream), three);
     }, py::arg("W"), py::arg("nrows_pad"), py::arg("nf"), py::arg("ldw"), py::arg("hi"), py::arg("lo"),
        py::arg("stream"), py::arg("three") = false);
-    m.def("mf_forward_b16", [](uintptr_t A, int64_t ld, int64_t nrows, int64_t nrows_pad, uintptr_t Xh, uintptr_t Xl,
-                               uintptr_t Fout, int nsplit, uintptr_t stream, int nf, bool xblk) {
-        sart::launch_mf_forward_b16(P<const sart::bf16_t>(A), ld, nrows, nrows_pad, P<const sart::bf16_t>(Xh),
-                                    P<const sart::bf16_t>(Xl), P<float>(Fout), nsplit, nf, S(stream), xblk);
+    m.def("mf_forward_b16", [fwd_plan](uintptr_t A, int64_t ld, int64_t nrows, int64_t nrows_pad, uintptr_t Xh,
+                                       uintptr_t Xl, uintptr_t Fout, int nsplit, uintptr_t stream, int nf, bool xblk) {
+        sart::launch_mf_forward_b16(fwd_plan(sart::MfPath::b16, nf, ld, nrows_pad, nsplit, "mf_forward_b16"),
+                                    P<const sart::bf16_t>(A), nrows, P<const sart::bf16_t>(Xh),
+                                    P<const sart::bf16_t>(Xl), P<float>(Fout), S(stream), xblk);
     }, py::arg("A"), py::arg("ld"), py::arg("nrows"), py::arg("nrows_pad"), py::arg("Xh"), py::arg("Xl"),
        py::arg("Fout"), py::arg("nsplit"), py::arg("stream"), py::arg("nf"), py::arg("xblk") = false);
-    m.def("mf_backproject_b16", [](uintptr_t A, int64_t ld, int64_t nrows, uintptr_t Wh, uintptr_t Wl, int64_t ldw,
-                                   int nsplit, uintptr_t partial, uintptr_t stream, int nf, int64_t v0, int64_t v1) {
-        sart::launch_mf_backproject_b16(P<const sart::bf16_t>(A), ld, nrows, P<const sart::bf16_t>(Wh),
-                                        P<const sart::bf16_t>(Wl), ldw, nsplit, P<float>(partial), nf, S(stream), v0,
-                                        v1);
+    m.def("mf_backproject_b16", [bwd_plan](uintptr_t A, int64_t ld, int64_t nrows, uintptr_t Wh, uintptr_t Wl,
+                                           int64_t ldw, int nsplit, uintptr_t partial, uintptr_t stream, int nf,
+                                           int64_t v0, int64_t v1) {
+        sart::launch_mf_backproject_b16(bwd_plan(sart::MfPath::b16, nf, ld, nrows, nsplit, "mf_backproject_b16"),
+                                        P<const sart::bf16_t>(A), P<const sart::bf16_t>(Wh),
+                                        P<const sart::bf16_t>(Wl), ldw, P<float>(partial), S(stream), v0, v1);
     }, py::arg("A"), py::arg("ld"), py::arg("nrows"), py::arg("Wh"), py::arg("Wl"), py::arg("ldw"), py::arg("nsplit"),
        py::arg("partial"), py::arg("stream"), py::arg("nf") = 16, py::arg("v0") = 0, py::arg("v1") = -1);
-    m.def("mf_backproject", [](uintptr_t A, int64_t ld, int64_t nrows, uintptr_t W, int nsplit, uintptr_t partial,
-                               uintptr_t stream, int nf) {
-        sart::launch_mf_backproject(P<const float>(A), ld, nrows, P<const float>(W), nsplit, P<float>(partial), nf,
-                                    S(stream));
+    m.def("mf_backproject", [bwd_plan](uintptr_t A, int64_t ld, int64_t nrows, uintptr_t W, int nsplit,
+                                       uintptr_t partial, uintptr_t stream, int nf) {
+        sart::launch_mf_backproject(bwd_plan(sart::MfPath::fp32, nf, ld, nrows, nsplit, "mf_backproject"),
+                                    P<const float>(A), P<const float>(W), P<float>(partial), S(stream));
     }, py::arg("A"), py::arg("ld"), py::arg("nrows"), py::arg("W"), py::arg("nsplit"), py::arg("partial"),
        py::arg("stream"), py::arg("nf") = 16);
 }

@@ -133,9 +133,16 @@ MultiFrameEngine::MultiFrameEngine(int device, const void* A, int64_t nrows, int
     xlast_.resize(ld_);
     xlast2_.resize(ld_);
     if (cfg_.logarithmic) oq_.resize((size_t)qcap_ * ld_);
-    nsf_ = mf_forward_num_splits(ld_, Pp_, bf16_ ? 512 : 0);  // bf16 storage: ~512 workgroups (see the back-projection)
-    nsb_ = split_ ? mf_backproject_b16_num_splits(ld_, P_, x3_) : mf_backproject_num_splits(ld_, P_);
-    if (sparse_) {  // the SpMM kernels write complete sums
+    if (!sparse_) {
+        // the launch plans of the two projections: the knobs are read here, once; buffer sizes, the chunk alignment
+        // and every launch come from these two objects
+        const MfKnobs knobs = MfKnobs::from_env();
+        const MfPath base = bf16_ ? MfPath::b16 : (x3_ ? MfPath::x3 : MfPath::fp32);
+        fplan_ = mf_plan_forward(fwd16_ ? MfPath::h16 : base, NF, ld_, Pp_, knobs);
+        bplan_ = mf_plan_backproject(h16_ ? MfPath::h16 : base, NF, ld_, P_, knobs);
+        nsf_ = fplan_.nsplit;
+        nsb_ = bplan_.nsplit;
+    } else {  // the SpMM kernels write complete sums
         nsf_ = nsb_ = 1;
         Xt_.resize((size_t)ld_ * NF);
         pw_ = mf_sparse_plane_width(NF);
@@ -190,7 +197,8 @@ MultiFrameEngine::MultiFrameEngine(int device, const void* A, int64_t nrows, int
         const int64_t min_vox = std::max<int64_t>(1, (1 << 20) / (4 * NF));
         nchunks = (int)std::max<int64_t>(1, std::min<int64_t>(nchunks, ld_ / min_vox));
     }
-    const int64_t align = split_ ? mf_backproject_b16_vox_align(ld_, x3_) : mf_backproject_vox_align(ld_, NF);
+    // (a sparse shard's SpMM has no voxel tile: 128 voxels from 32 frames on where the row allows, as the fp32 kernels)
+    const int64_t align = sparse_ ? (NF >= 32 && ld_ % 128 == 0 ? 128 : 64) : bplan_.vox_align;
     chunks_.assign(1, 0);
     for (int c = 1; c < nchunks; ++c) {
         const int64_t v = (ld_ * c / nchunks) / align * align;
@@ -267,20 +275,20 @@ void MultiFrameEngine::forward() {
         uint16_t* x1 = reinterpret_cast<uint16_t*>(Xh_.get());
         uint16_t* x2 = reinterpret_cast<uint16_t*>(Xl_.get());
         launch_mf_split_x16(X_.get(), ld_, nf_, x1, x2, xmax_.get(), xinv_.get(), stream_, true, xblk_);
-        launch_mf_forward_h16(static_cast<const float*>(A_), ld_, P_, Pp_, x1, x2, Fs_.get(), nsf_, nf_, stream_, xblk_,
-                              rsc_.get(), xinv_.get());
+        launch_mf_forward_h16(fplan_, static_cast<const float*>(A_), P_, x1, x2, Fs_.get(), stream_, xblk_, rsc_.get(),
+                              xinv_.get());
         return;
     }
     if (split_) {
         launch_mf_split_x(X_.get(), (int64_t)nf_ * ld_, Xh_.get(), Xl_.get(), stream_, x3_, xblk_ ? ld_ : 0);
         if (bf16_)
-            launch_mf_forward_b16(static_cast<const bf16_t*>(A_), ld_, P_, Pp_, Xh_.get(), Xl_.get(), Fs_.get(), nsf_,
-                                  nf_, stream_, xblk_);
+            launch_mf_forward_b16(fplan_, static_cast<const bf16_t*>(A_), P_, Xh_.get(), Xl_.get(), Fs_.get(), stream_,
+                                  xblk_);
         else
-            launch_mf_forward_x3(static_cast<const float*>(A_), ld_, P_, Pp_, Xh_.get(), Xl_.get(), Fs_.get(), nsf_,
-                                 nf_, stream_, xblk_);
+            launch_mf_forward_x3(fplan_, static_cast<const float*>(A_), P_, Xh_.get(), Xl_.get(), Fs_.get(), stream_,
+                                 xblk_);
     } else {
-        launch_mf_forward(static_cast<const float*>(A_), ld_, P_, Pp_, X_.get(), ld_, Fs_.get(), nsf_, nf_, stream_);
+        launch_mf_forward(fplan_, static_cast<const float*>(A_), P_, X_.get(), Fs_.get(), stream_);
     }
 }
 
@@ -302,18 +310,18 @@ void MultiFrameEngine::backproject(const float* W, bool split_w, int64_t v0, int
         uint16_t* w2 = W16_.get() + (size_t)nf_ * Pp_;
         if (split_w)
             launch_mf_split_w16(W, Pp_, nf_, Pp_, w1, w2, wmax_.get(), 1.f, wscale_.get(), stream_, have_max);
-        launch_mf_backproject_h16(static_cast<const float*>(A_), ld_, P_, w1, w2, Pp_, nsb_, part_.get(), nf_, stream_,
-                                  v0, v1, csc_.get(), wscale_.get());
+        launch_mf_backproject_h16(bplan_, static_cast<const float*>(A_), w1, w2, Pp_, part_.get(), stream_, v0, v1,
+                                  csc_.get(), wscale_.get());
     } else if (split_) {
         if (split_w) launch_mf_split_w(W, Pp_, nf_, Pp_, Wh_.get(), Wl_.get(), stream_, x3_);
         if (bf16_)
-            launch_mf_backproject_b16(static_cast<const bf16_t*>(A_), ld_, P_, Wh_.get(), Wl_.get(), Pp_, nsb_,
-                                      part_.get(), nf_, stream_, v0, v1);
+            launch_mf_backproject_b16(bplan_, static_cast<const bf16_t*>(A_), Wh_.get(), Wl_.get(), Pp_, part_.get(),
+                                      stream_, v0, v1);
         else
-            launch_mf_backproject_x3(static_cast<const float*>(A_), ld_, P_, Wh_.get(), Wl_.get(), Pp_, nsb_,
-                                     part_.get(), nf_, stream_, v0, v1);
+            launch_mf_backproject_x3(bplan_, static_cast<const float*>(A_), Wh_.get(), Wl_.get(), Pp_, part_.get(),
+                                     stream_, v0, v1);
     } else {
-        launch_mf_backproject(static_cast<const float*>(A_), ld_, P_, W, nsb_, part_.get(), nf_, stream_, v0, v1);
+        launch_mf_backproject(bplan_, static_cast<const float*>(A_), W, part_.get(), stream_, v0, v1);
     }
 }
 

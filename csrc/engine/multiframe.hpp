@@ -20,6 +20,7 @@
 #include "../native/solver_params.hpp"
 #include "comm.hpp"
 #include "engine.hpp"
+#include "mf_plan.hpp"
 
 namespace sart {
 
@@ -126,6 +127,8 @@ class MultiFrameEngine {
     EngineConfig cfg_;
     hipStream_t stream_ = nullptr;
     int nf_ = 16;
+    MfFwdPlan fplan_;  // the projections' launch plans, made once in the constructor (dense shards)
+    MfBwdPlan bplan_;
     int nsf_ = 1, nsb_ = 1, nwb_ = 1;
     DeviceRaySums rs_;
     DeviceArray<float> X_, Xprev_, Fs_, W_, part_, buf_, pen_, O_, ghat_, arow_, gpos_, wo_;

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "sart_common.hpp"
+#include "../engine/mf_plan.hpp"
 
 namespace sart {
 // projection.hip (RTM in fp32, or bf16 storage with fp32 products and sums)
@@ -210,18 +211,13 @@ void launch_p2p_reduce_allreduce(const ReduceSrc& src, float* out, const P2pArgs
                                  unsigned epoch, int64_t cap, unsigned* err, double timeout_s, hipStream_t stream,
                                  bool skip_flags = false, const UpdateArgs* upd = nullptr);
 // multiframe.hip (nf = frames per batch: 16, 32 or 64; the 16-bit kernels of multiframe_bf16.hip also take 128)
-// target: workgroups to aim for (0: 1024, or SART_MF_FWD_BLOCKS)
-int mf_forward_num_splits(int64_t ld, int64_t nrows_pad, int target = 0);
-int mf_backproject_num_splits(int64_t ld, int64_t nrows);
-void mf_set_depth(int d);  // 1..3: register-ring depth of the MFMA projections; 0: default
-void mf_set_rows(int rt);  // 2 or 4: 16-row tiles per wave of the MFMA forward projection; 0: default
-void mf_set_vox(int vt);   // 1 or 2: 64-voxel tiles per wave of the MFMA back-projection; 0: default
-void launch_mf_forward(const float* A, int64_t ld, int64_t nrows, int64_t nrows_pad, const float* X, int64_t ldx,
-                       float* Fout, int nsplit, int nf, hipStream_t stream);
-// voxel range [v0, v1) (default: the whole row), aligned to mf_backproject_vox_align
-int mf_backproject_vox_align(int64_t ld, int nf);
-void launch_mf_backproject(const float* A, int64_t ld, int64_t nrows, const float* W, int nsplit, float* partial,
-                           int nf, hipStream_t stream, int64_t v0 = 0, int64_t v1 = -1);
+// The launchers of the MFMA projections take the plan of their path (engine/mf_plan.hpp: kernel variant, grid,
+// split-K; mf_plan_forward / mf_plan_backproject); shapes, tunables and split counts are the plan's. X: [nf][ld].
+void launch_mf_forward(const MfFwdPlan& p, const float* A, int64_t nrows, const float* X, float* Fout,
+                       hipStream_t stream);
+// voxel range [v0, v1) (default: the whole row), aligned to the wave's voxel tile (the plan's vox_align is)
+void launch_mf_backproject(const MfBwdPlan& p, const float* A, const float* W, float* partial, hipStream_t stream,
+                           int64_t v0 = 0, int64_t v1 = -1);
 // multiframe_glue.hip
 // No-op sweeps of the multi-frame engine: while a MfSkipScope is alive on the calling thread, the heavy multi-frame
 // kernels (projections, weights, collect, operand splits) launched from it return at once when *skip != 0 (the
@@ -238,20 +234,16 @@ struct MfSkipScope {
 // operand (X or W) split into hi + lo bf16 planes (k_mf_split_x: X [nf][ld] -> planes [nf][ld]; k_mf_split_w:
 // W [rows][16][nf / 16] -> frame-major planes [nf][ldw], ldw >= rows rounded up to 32).
 // xblk: X planes in the blocked layout [ld / 32][nf][32] (launch_mf_split_x with ld > 0), else frame-major [nf][ld]
-void launch_mf_forward_b16(const bf16_t* A, int64_t ld, int64_t nrows, int64_t nrows_pad, const bf16_t* Xh,
-                           const bf16_t* Xl, float* Fout, int nsplit, int nf, hipStream_t stream, bool xblk = false);
-// a32: the split-A kernels (fp32 A split into hi + lo bf16 in registers, three products; launch_mf_*_x3)
-int mf_backproject_b16_num_splits(int64_t ld, int64_t nrows, bool a32 = false);
-int mf_backproject_b16_vox_align(int64_t ld, bool a32 = false);  // voxel-range alignment of the launchers below
-void launch_mf_backproject_b16(const bf16_t* A, int64_t ld, int64_t nrows, const bf16_t* Wh, const bf16_t* Wl,
-                               int64_t ldw, int nsplit, float* partial, int nf, hipStream_t stream, int64_t v0 = 0,
-                               int64_t v1 = -1);
-void launch_mf_forward_x3(const float* A, int64_t ld, int64_t nrows, int64_t nrows_pad, const bf16_t* Xh,
-                          const bf16_t* Xl, float* Fout, int nsplit, int nf, hipStream_t stream, bool xblk = false);
+void launch_mf_forward_b16(const MfFwdPlan& p, const bf16_t* A, int64_t nrows, const bf16_t* Xh, const bf16_t* Xl,
+                           float* Fout, hipStream_t stream, bool xblk = false);
+void launch_mf_backproject_b16(const MfBwdPlan& p, const bf16_t* A, const bf16_t* Wh, const bf16_t* Wl, int64_t ldw,
+                               float* partial, hipStream_t stream, int64_t v0 = 0, int64_t v1 = -1);
+// the split-A kernels (fp32 A split into hi + lo bf16 in registers, three products)
+void launch_mf_forward_x3(const MfFwdPlan& p, const float* A, int64_t nrows, const bf16_t* Xh, const bf16_t* Xl,
+                          float* Fout, hipStream_t stream, bool xblk = false);
 // Wh: hi and mid planes ([2][nf][ldw], launch_mf_split_w with three), Wl: lo plane
-void launch_mf_backproject_x3(const float* A, int64_t ld, int64_t nrows, const bf16_t* Wh, const bf16_t* Wl,
-                              int64_t ldw, int nsplit, float* partial, int nf, hipStream_t stream, int64_t v0 = 0,
-                              int64_t v1 = -1);
+void launch_mf_backproject_x3(const MfBwdPlan& p, const float* A, const bf16_t* Wh, const bf16_t* Wl, int64_t ldw,
+                              float* partial, hipStream_t stream, int64_t v0 = 0, int64_t v1 = -1);
 // perm: the split-A forward's k order (launch_mf_forward_x3 reads planes written with perm = true). ld > 0: X is
 // [nf = n / ld][ld] and the planes are written blocked, [ld / 32][nf][32] (the forward's xblk layout)
 void launch_mf_split_x(const float* X, int64_t n, bf16_t* hi, bf16_t* lo, hipStream_t stream, bool perm = false,
@@ -266,9 +258,9 @@ float absmax_pow2_scale(const float* A, int64_t n, unsigned* scratch, hipStream_
 // split-A back-projection on f16 pairs (two pieces of A s_v and of W s_f, three v_mfma_f32_16x16x32_f16 products,
 // fp32 accumulation, the output scaled by 1 / s_v and inv_scale[f] = 1 / s_f): W1 / W2 from launch_mf_split_w16
 // (a_scale 1), csc from launch_mf_col_scales
-void launch_mf_backproject_h16(const float* A, int64_t ld, int64_t nrows, const uint16_t* W1, const uint16_t* W2,
-                               int64_t ldw, int nsplit, float* partial, int nf, hipStream_t stream, int64_t v0,
-                               int64_t v1, const float* csc, const float* inv_scale);
+void launch_mf_backproject_h16(const MfBwdPlan& p, const float* A, const uint16_t* W1, const uint16_t* W2, int64_t ldw,
+                               float* partial, hipStream_t stream, int64_t v0, int64_t v1, const float* csc,
+                               const float* inv_scale);
 // Range-safe f16 scales (multiframe_glue.hip): powers of two per row (rsc: [nrows_pad] scales then their inverses)
 // and per column (csc: [ld] then [ld]; scratch: ld words) of an fp32 shard
 void launch_mf_row_scales(const float* A, int64_t ld, int64_t nrows_pad, float* rsc, hipStream_t stream);
@@ -280,9 +272,8 @@ void launch_mf_split_x16(const float* X, int64_t ld, int nf, uint16_t* x1, uint1
                          hipStream_t stream, bool perm, bool blocked);
 // split-A forward on f16 pairs: A s_p (rsc, per row) times X s_f (launch_mf_split_x16), three f16 products, the
 // output scaled by 1 / (s_p s_f)
-void launch_mf_forward_h16(const float* A, int64_t ld, int64_t nrows, int64_t nrows_pad, const uint16_t* X1,
-                           const uint16_t* X2, float* Fout, int nsplit, int nf, hipStream_t stream, bool xblk,
-                           const float* rsc, const float* xinv);
+void launch_mf_forward_h16(const MfFwdPlan& p, const float* A, int64_t nrows, const uint16_t* X1, const uint16_t* X2,
+                           float* Fout, hipStream_t stream, bool xblk, const float* rsc, const float* xinv);
 // three: hi [nf][ldw] then mid [nf][ldw] in `hi` (2 nf ldw elements), lo: the split-A back-projection's planes
 void launch_mf_split_w(const float* W, int64_t nrows_pad, int nf, int64_t ldw, bf16_t* hi, bf16_t* lo,
                        hipStream_t stream, bool three = false);

@@ -28,6 +28,7 @@
 //   C/D: col = l & 15, row = (l >> 4) * 4 + reg.
 #include "sart_common.hpp"
 #include "launchers.hpp"
+#include "../engine/mf_variants.hpp"
 
 #include <cstdlib>
 #include <stdexcept>
@@ -324,184 +325,43 @@ __global__ __launch_bounds__(256) void k_mf_backproject(const float* __restrict_
             }
 }
 
-// Split-K of the forward projection: >= ~1024 workgroups, >= 1024 columns per split. (Splitting further
-// so that a split's X chunk stays L2-resident measured 0-9 % slower at nf = 16..64, 64k x 64k.)
-static int mf_rows(int nf);
-int mf_forward_num_splits(int64_t ld, int64_t nrows_pad, int target_blocks) {
-    const int64_t rows_per_block = (nrows_pad % 64 == 0 ? mf_rows(0) : 2) * 64;  // 4 waves x 16 * rt rows
-    const int64_t nblk = (nrows_pad + rows_per_block - 1) / rows_per_block;
-    const char* e = std::getenv("SART_MF_FWD_BLOCKS");  // target workgroups (tuning knob)
-    const int64_t target = (e && *e) ? std::atoll(e) : (target_blocks > 0 ? target_blocks : 1024);
-    int64_t s = (target + nblk - 1) / nblk;
-    const int64_t smax = ld / 1024;
-    if (s > smax) s = smax;
-    if (s < 1) s = 1;
-    return (int)s;
-}
+// ------------------------------------------------------------------ launch: a table lookup per kernel signature
+// (variant lists: engine/mf_variants.hpp; depth, tiles and split counts: the planner, engine/mf_plan.cpp)
+namespace {
+typedef void (*FwdFn)(const float*, int64_t, int64_t, int64_t, const float*, int64_t, float*, int64_t, const int*);
+typedef void (*BwdFn)(const float*, int64_t, int64_t, const float*, int64_t, float*, int64_t, int64_t, const int*);
 
-static int mf_vox(int64_t ld, int nf);
-// Split-K of the back-projection: ~512 workgroups. The kernel time is flat from 4 to 32 splits at
-// 64k x 64k (profiles/probe_r1_mf_splits.jsonl) while k_mf_collect reads nsplit partial slices.
-int mf_backproject_num_splits(int64_t ld, int64_t nrows) {
-    const int64_t nblk = (ld / (64 * mf_vox(ld, 64)) + 3) / 4;  // the fp32 kernels' widest batch
-    const char* e = std::getenv("SART_MF_BP_BLOCKS");  // target workgroups (tuning knob)
-    // 2048 (4 x the 512 of round 1): a split's rows are one fp32 MFMA accumulation chain; 16k-row splits at 64k x 64k
-    // were the larger share of the multi-frame engine's error against the fp32 two-pass kernels
-    // (profiles/parity_r6_64k_mf_chains.jsonl); the extra partial slices cost k_mf_collect ~1.5 % of a sweep
-    const int64_t target = (e && *e) ? std::atoll(e) : 2048;
-    int64_t s = (target + nblk - 1) / nblk;
-    const int64_t smax = (nrows + 63) / 64;
-    if (s > smax) s = smax;
-    if (s < 1) s = 1;
-    return (int)s;
-}
+const MfVariant<FwdFn> kFwd[] = {
+#define X(NG, D, RT, NT) {mf_key_fwd_f32(NG, D, RT, NT), k_mf_forward<NG, D, RT, NT>},
+    MF_FWD_F32_VARIANTS(X)
+#undef X
+};
+const MfVariant<BwdFn> kBwd[] = {
+#define X(NG, D, VT) {mf_key_bwd_f32(NG, D, VT), k_mf_backproject<NG, D, VT>},
+    MF_BWD_F32_VARIANTS(X)
+#undef X
+};
+}  // namespace
 
-static void check_nf(int nf, const char* what) {
-    if (nf != 16 && nf != 32 && nf != 64) throw std::runtime_error(std::string(what) + ": nf must be 16, 32 or 64");
-}
-
-// Register-ring depth (steps of loads in flight per wave). Defaults per kernel and batch width from
-// tools/probe_mf.py on 64k x 64k (profiles/probe_r1_mf_tiles.jsonl, with the default tilings below: forward
-// 64 rows per wave, back-projection 64 voxels per wave at nf = 16 and 128 at nf = 32 / 64); SART_MF_DEPTH=1..3
-// or mf_set_depth() overrides them.
-static int g_mf_depth = -1;
-void mf_set_depth(int d) { g_mf_depth = d; }
-static int mf_depth(bool forward, int nf) {
-    if (g_mf_depth < 0) {
-        const char* e = std::getenv("SART_MF_DEPTH");
-        g_mf_depth = (e && *e) ? std::atoi(e) : 0;
-    }
-    if (g_mf_depth >= 1 && g_mf_depth <= 3) return g_mf_depth;
-    if (forward) return nf == 64 ? 2 : 3;           // with 64-row waves (profiles/probe_r1_mf_tiles.jsonl)
-    return nf == 32 ? 1 : 2;                         // nf 16: 64-voxel waves; nf 32 / 64: 128-voxel waves
-}
-
-// 64-voxel tiles per wave of the back-projection: 1 or 2 (ld % 128 == 0); SART_MF_VOX or mf_set_vox().
-static int g_mf_vox = -1;
-void mf_set_vox(int vt) { g_mf_vox = vt; }
-static int mf_vox(int64_t ld, int nf) {
-    if (g_mf_vox < 0) {
-        const char* e = std::getenv("SART_MF_VOX");
-        g_mf_vox = (e && *e) ? std::atoi(e) : 0;
-    }
-    const int vt = (g_mf_vox == 1 || g_mf_vox == 2) ? g_mf_vox : (nf >= 32 ? 2 : 1);
-    return (vt == 2 && ld % 128 == 0) ? 2 : 1;
-}
-
-// Row tiles per wave of the forward kernel: 2 (32 rows) or 4 (64 rows); SART_MF_ROWS or mf_set_rows().
-static int g_mf_rows = -1;
-void mf_set_rows(int rt) { g_mf_rows = rt; }
-static int mf_rows(int nf) {
-    if (g_mf_rows < 0) {
-        const char* e = std::getenv("SART_MF_ROWS");
-        g_mf_rows = (e && *e) ? std::atoi(e) : 0;
-    }
-    if (g_mf_rows == 2 || g_mf_rows == 4) return g_mf_rows;
-    (void)nf;
-    return 4;
-}
-
-template <int NG, int RT, bool NT>
-static void fwd_rt_nt(dim3 grid, int depth, hipStream_t stream, const float* A, int64_t ld, int64_t nrows,
-                      int64_t nrows_pad, const float* X, int64_t ldx, float* Fout, int64_t cps) {
-    if (depth == 1)
-        hipLaunchKernelGGL((k_mf_forward<NG, 1, RT, NT>), grid, dim3(256), 0, stream, A, ld, nrows, nrows_pad, X, ldx, Fout, cps, g_mf_skip);
-    else if (depth == 3)
-        hipLaunchKernelGGL((k_mf_forward<NG, 3, RT, NT>), grid, dim3(256), 0, stream, A, ld, nrows, nrows_pad, X, ldx, Fout, cps, g_mf_skip);
-    else
-        hipLaunchKernelGGL((k_mf_forward<NG, 2, RT, NT>), grid, dim3(256), 0, stream, A, ld, nrows, nrows_pad, X, ldx, Fout, cps, g_mf_skip);
-}
-
-// Non-temporal A loads in the MFMA forward (experiment knob, SART_MF_NT=1; default plain loads).
-static int mf_nt() {
-    static int v = -1;
-    if (v < 0) {
-        const char* e = std::getenv("SART_MF_NT");
-        v = (e && *e) ? std::atoi(e) : 0;
-    }
-    return v;
-}
-
-template <int NG, int RT>
-static void fwd_rt(dim3 grid, int depth, hipStream_t stream, const float* A, int64_t ld, int64_t nrows,
-                   int64_t nrows_pad, const float* X, int64_t ldx, float* Fout, int64_t cps) {
-    if (mf_nt() == 1)
-        fwd_rt_nt<NG, RT, true>(grid, depth, stream, A, ld, nrows, nrows_pad, X, ldx, Fout, cps);
-    else
-        fwd_rt_nt<NG, RT, false>(grid, depth, stream, A, ld, nrows, nrows_pad, X, ldx, Fout, cps);
-}
-
-template <int NG>
-static void fwd(int rt, int depth, hipStream_t stream, const float* A, int64_t ld, int64_t nrows, int64_t nrows_pad,
-                const float* X, int64_t ldx, float* Fout, int nsplit, int64_t cps) {
-    const dim3 grid((unsigned)((nrows_pad + 64 * rt - 1) / (64 * rt)), (unsigned)nsplit);
-    if (rt == 4)
-        fwd_rt<NG, 4>(grid, depth, stream, A, ld, nrows, nrows_pad, X, ldx, Fout, cps);
-    else
-        fwd_rt<NG, 2>(grid, depth, stream, A, ld, nrows, nrows_pad, X, ldx, Fout, cps);
-}
-
-void launch_mf_forward(const float* A, int64_t ld, int64_t nrows, int64_t nrows_pad, const float* X, int64_t ldx,
-                       float* Fout, int nsplit, int nf, hipStream_t stream) {
-    if (ld % 64 != 0 || ldx != ld) throw std::runtime_error("mf_forward: ld must be a multiple of 64 and ldx == ld");
-    if (nrows_pad % 32 != 0) throw std::runtime_error("mf_forward: padded rows must be a multiple of 32");
-    if (nsplit < 1) throw std::runtime_error("mf_forward: nsplit must be >= 1");
-    check_nf(nf, "mf_forward");
-    const int64_t cps = ((ld + nsplit - 1) / nsplit + 15) / 16 * 16;
-    const int d = mf_depth(true, nf);
-    const int rt = (nrows_pad % 64 == 0) ? mf_rows(nf) : 2;  // a wave's 16 * rt rows lie inside the padding
-    if (nf == 16)
-        fwd<1>(rt, d, stream, A, ld, nrows, nrows_pad, X, ldx, Fout, nsplit, cps);
-    else if (nf == 32)
-        fwd<2>(rt, d, stream, A, ld, nrows, nrows_pad, X, ldx, Fout, nsplit, cps);
-    else
-        fwd<4>(rt, d, stream, A, ld, nrows, nrows_pad, X, ldx, Fout, nsplit, cps);
+void launch_mf_forward(const MfFwdPlan& p, const float* A, int64_t nrows, const float* X, float* Fout,
+                       hipStream_t stream) {
+    if (p.key.path != MfPath::fp32 || !p.key.forward)
+        throw std::runtime_error("mf_forward: the plan was made for another path");
+    hipLaunchKernelGGL(mf_variant(kFwd, p.key, "mf_forward"), dim3(p.grid_x, (unsigned)p.nsplit), dim3(256), 0, stream,
+                       A, p.ld, nrows, p.nrows_pad, X, p.ld, Fout, p.cps, g_mf_skip);
     check_launch("k_mf_forward");
 }
 
-template <int NG, int VT>
-static void bwd_vt(dim3 grid, int depth, hipStream_t stream, const float* A, int64_t ld, int64_t nrows, const float* W,
-                   int64_t rps, float* partial, int64_t vb0, int64_t vend) {
-    if (depth == 1)
-        hipLaunchKernelGGL((k_mf_backproject<NG, 1, VT>), grid, dim3(256), 0, stream, A, ld, nrows, W, rps, partial,
-                           vb0, vend, g_mf_skip);
-    else if (depth == 3)
-        hipLaunchKernelGGL((k_mf_backproject<NG, 3, VT>), grid, dim3(256), 0, stream, A, ld, nrows, W, rps, partial,
-                           vb0, vend, g_mf_skip);
-    else
-        hipLaunchKernelGGL((k_mf_backproject<NG, 2, VT>), grid, dim3(256), 0, stream, A, ld, nrows, W, rps, partial,
-                           vb0, vend, g_mf_skip);
-}
-
-template <int NG>
-static void bwd(int vt, int depth, hipStream_t stream, const float* A, int64_t ld, int64_t nrows, const float* W,
-                int nsplit, int64_t rps, float* partial, int64_t v0, int64_t v1) {
-    const int64_t vb0 = v0 / (64 * vt), nvb = (v1 - v0 + 64 * vt - 1) / (64 * vt);
-    const dim3 grid((unsigned)((nvb + 3) / 4), (unsigned)nsplit);
-    if (vt == 2)
-        bwd_vt<NG, 2>(grid, depth, stream, A, ld, nrows, W, rps, partial, vb0, v1);
-    else
-        bwd_vt<NG, 1>(grid, depth, stream, A, ld, nrows, W, rps, partial, vb0, v1);
-}
-
-int mf_backproject_vox_align(int64_t ld, int nf) { return 64 * mf_vox(ld, nf); }
-
-void launch_mf_backproject(const float* A, int64_t ld, int64_t nrows, const float* W, int nsplit, float* partial,
-                           int nf, hipStream_t stream, int64_t v0, int64_t v1) {
-    if (ld % 64 != 0) throw std::runtime_error("mf_backproject: ld must be a multiple of 64");
-    check_nf(nf, "mf_backproject");
-    if (v1 < 0) v1 = ld;
-    const int vt = mf_vox(ld, nf);
-    if (v0 < 0 || v1 > ld || v0 >= v1 || v0 % (64 * vt) != 0 || (v1 != ld && v1 % (64 * vt) != 0))
+void launch_mf_backproject(const MfBwdPlan& p, const float* A, const float* W, float* partial, hipStream_t stream,
+                           int64_t v0, int64_t v1) {
+    if (p.key.path != MfPath::fp32 || p.key.forward)
+        throw std::runtime_error("mf_backproject: the plan was made for another path");
+    if (v1 < 0) v1 = p.ld;
+    const int64_t tile = 64 * p.key.tile;
+    if (v0 < 0 || v1 > p.ld || v0 >= v1 || v0 % tile != 0 || (v1 != p.ld && v1 % tile != 0))
         throw std::runtime_error("mf_backproject: voxel range must be aligned to the wave's voxel tile");
-    const int64_t rps = ((nrows + nsplit - 1) / nsplit + 15) / 16 * 16;
-    const int d = mf_depth(false, nf);
-    if (nf == 16)
-        bwd<1>(vt, d, stream, A, ld, nrows, W, nsplit, rps, partial, v0, v1);
-    else if (nf == 32)
-        bwd<2>(vt, d, stream, A, ld, nrows, W, nsplit, rps, partial, v0, v1);
-    else
-        bwd<4>(vt, d, stream, A, ld, nrows, W, nsplit, rps, partial, v0, v1);
+    hipLaunchKernelGGL(mf_variant(kBwd, p.key, "mf_backproject"), dim3(p.grid_x(v0, v1), (unsigned)p.nsplit), dim3(256),
+                       0, stream, A, p.ld, p.nrows, W, p.rps, partial, v0 / tile, v1, g_mf_skip);
     check_launch("k_mf_backproject");
 }
 

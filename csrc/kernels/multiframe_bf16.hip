@@ -39,6 +39,7 @@
 // fp32 sums are those of the fp32 engine.
 #include "sart_common.hpp"
 #include "launchers.hpp"
+#include "../engine/mf_variants.hpp"
 
 #include <cstdlib>
 #include <cstring>
@@ -320,14 +321,11 @@ __global__ __launch_bounds__(256) void k_mf_forward_b16(const bf16_t* __restrict
 template <typename AT, int NG>
 constexpr int mf_fwd_min_waves() { return std::is_same<AT, float>::value ? 1 : (NG == 4 ? SART_MF_MINW_FWD : 1); }
 
-// ABL: diagnostic ablations as in k_mf_backproject_b16_lds (bit 0 no MFMAs, bit 1 no split of A, bit 2 no X staging
-// and no barrier); 0 in every production launch.
 // EX (early X): X of step u is loaded at step u - DEPTH - 1, ahead of A's batch (see EW of k_mf_backproject_b16_lds).
 // H16 (split-A only): A enters as two f16 pieces of A s_p (s_p per row, FwdCols::rsc) and X as two f16 pieces of
 // X s_f (launch_mf_split_x16), three v_mfma_f32_16x16x32_f16 products (a2 x1, a1 x2, a1 x1), the epilogue multiplies
 // by 1 / (s_p s_f): 2^-22 per product instead of the 2^-17 of the bf16 hi + lo pieces, at the same cost.
-template <int NG, int DEPTH, int RT, int KB, typename AT = bf16_t, bool AS = false, int ABL = 0, bool EX = false,
-          bool H16 = false>
+template <int NG, int DEPTH, int RT, int KB, typename AT = bf16_t, bool AS = false, bool EX = false, bool H16 = false>
 __global__ __launch_bounds__(256, (mf_fwd_min_waves<AT, NG>())) void k_mf_forward_b16_lds(const AT* __restrict__ A, int64_t ld, int64_t nrows,
                                                             int64_t nrows_pad, const bf16_t* __restrict__ Xh,
                                                             const bf16_t* __restrict__ Xl, float* __restrict__ Fout,
@@ -368,7 +366,7 @@ __global__ __launch_bounds__(256, (mf_fwd_min_waves<AT, NG>())) void k_mf_forwar
     static_assert(!AS || R16 >= 8, "A staging needs full 128-B row segments");
     __shared__ __attribute__((aligned(16))) u32x4 s_a[AS ? 4 : 1][AS ? 16 * RT * R16 : 1];
     const AT* __restrict__ asp = A + (row0 + lane / R16) * ld + c0 + (lane % R16) * (16 / (int)sizeof(AT));
-    static_assert(!H16 || (A32 && ABL == 0), "the f16-pair forward is a split-A kernel");
+    static_assert(!H16 || A32, "the f16-pair forward is a split-A kernel");
     float rs[RT];  // H16: this lane's row scales (row row0 + 16 rt + r of each row tile)
 #pragma unroll
     for (int rt = 0; rt < RT; ++rt) rs[rt] = H16 ? fc.rsc[row0 + rt * 16 + r] : 1.f;
@@ -477,8 +475,8 @@ __global__ __launch_bounds__(256, (mf_fwd_min_waves<AT, NG>())) void k_mf_forwar
                 if constexpr (LATE) __builtin_amdgcn_sched_barrier(0);
                 stage(std::integral_constant<int, (sl + 1) % RS>{}, t + 1);
             };
-            if constexpr (!LATE && !(ABL & 4)) stage_next();
-            const u32x4* xs = s_x[(ABL & 4) ? 0 : (t & 1)][0] + lofs;
+            if constexpr (!LATE) stage_next();
+            const u32x4* xs = s_x[t & 1][0] + lofs;
             u32x4* img = s_a[AS ? wave : 0];
             if constexpr (AS) {  // this wave's tile into its LDS image (swizzled slots)
 #pragma unroll
@@ -522,21 +520,16 @@ __global__ __launch_bounds__(256, (mf_fwd_min_waves<AT, NG>())) void k_mf_forwar
                     u32x4 ah[RT], al[RT];
 #pragma unroll
                     for (int rt = 0; rt < RT; ++rt) {
-                        if constexpr (AS && (ABL & 2)) {
-                            ah[rt] = frag16(rt, kb * 8 + g);
-                            al[rt] = frag16(rt, kb * 8 + 4 + g);
-                        } else {
-                            u32x8 v;
-                            if constexpr (AS)
-                                v = __builtin_shufflevector(frag16(rt, kb * 8 + g), frag16(rt, kb * 8 + 4 + g), 0, 1, 2,
-                                                            3, 4, 5, 6, 7);
-                            else
-                                v = a[sl][rt][kb];
-                            if constexpr (H16)
-                                split_h8(v, rs[rt], ah[rt], al[rt]);
-                            else
-                                split_a8(v, ah[rt], al[rt]);
-                        }
+                        u32x8 v;
+                        if constexpr (AS)
+                            v = __builtin_shufflevector(frag16(rt, kb * 8 + g), frag16(rt, kb * 8 + 4 + g), 0, 1, 2, 3,
+                                                        4, 5, 6, 7);
+                        else
+                            v = a[sl][rt][kb];
+                        if constexpr (H16)
+                            split_h8(v, rs[rt], ah[rt], al[rt]);
+                        else
+                            split_a8(v, ah[rt], al[rt]);
                     }
                     u32x4 xh[NG], xl[NG];
 #pragma unroll
@@ -545,13 +538,6 @@ __global__ __launch_bounds__(256, (mf_fwd_min_waves<AT, NG>())) void k_mf_forwar
                         xl[j] = xs[((kb * 2 + 1) * NG + j) * 64];
                     }
                     // product-major: consecutive MFMAs write different accumulators (no dependent chains)
-                    if constexpr ((ABL & 1) != 0) {
-#pragma unroll
-                        for (int j = 0; j < NG; ++j)
-#pragma unroll
-                            for (int rt = 0; rt < RT; ++rt)
-                                acc[rt][j][0] += __uint_as_float((al[rt][0] ^ ah[rt][3] ^ xh[j][1] ^ xl[j][2]) & 0x3fffffu);
-                    } else {
                     auto mm = [](const u32x4 p, const u32x4 q, floatx4 c) {
                         if constexpr (H16) return mfma_h16(p, q, c);
                         else return mfma_b16(p, q, c);
@@ -568,7 +554,6 @@ __global__ __launch_bounds__(256, (mf_fwd_min_waves<AT, NG>())) void k_mf_forwar
                     for (int j = 0; j < NG; ++j)
 #pragma unroll
                         for (int rt = 0; rt < RT; ++rt) acc[rt][j] = mm(ah[rt], xh[j], acc[rt][j]);
-                    }
                 } else if constexpr (AS) {
                     u32x4 af[RT];
 #pragma unroll
@@ -596,7 +581,6 @@ __global__ __launch_bounds__(256, (mf_fwd_min_waves<AT, NG>())) void k_mf_forwar
                     }
                 }
             }
-            if constexpr (ABL & 4) return;
             if constexpr (LATE) stage_next();
             __syncthreads();
         };
@@ -745,15 +729,11 @@ constexpr int mf_bwd_min_waves() {
     return std::is_same<AT, float>::value ? (VT == 1 ? 2 : 1) : SART_MF_MINW_BWD;
 }
 
-// ABL (diagnostic ablations, tools/probe_mf_x3.py with SART_MF_ABL; 0 in every production launch): bit 0 drops the
-// MFMAs (each fragment folds into an accumulator with one VALU op, so no load is dead), bit 1 drops the split of A
-// (split-A: the raw bits stand for all three pieces), bit 2 drops the W staging (no LDS writes, no barrier: the step
-// re-reads the stage of step 0). Times of the ablated kernels locate the pipe that bounds a step.
 // EW (early W): W of step u is loaded one step before A of step u's batch would be (at step u - DEPTH - 1, into ring
 // slot u % RS, whose previous W was staged the step before). The wait that staging step t + 1's W needs then covers
 // only loads issued at step t - DEPTH or earlier; loaded in one batch with A of step t + 1 (EW false), that wait also
 // held every wave until A of step t + 1 had arrived, i.e. one step ahead instead of DEPTH (in-order vmcnt).
-template <int NG, int DEPTH, int VT, typename AT = bf16_t, int ABL = 0, bool EW = false>
+template <int NG, int DEPTH, int VT, typename AT = bf16_t, bool EW = false>
 __global__ __launch_bounds__(256, (NG == 4 ? mf_bwd_min_waves<AT, VT>() : (std::is_same<AT, float>::value && VT == 1 ? 2 : 1))) void k_mf_backproject_b16_lds(const AT* __restrict__ A, int64_t ld,
                                                                 int64_t nrows32, const bf16_t* __restrict__ Wh,
                                                                 const bf16_t* __restrict__ Wl, int64_t ldw,
@@ -848,8 +828,8 @@ __global__ __launch_bounds__(256, (NG == 4 ? mf_bwd_min_waves<AT, VT>() : (std::
                 if constexpr (LATE) __builtin_amdgcn_sched_barrier(0);
                 stage(std::integral_constant<int, (sl + 1) % RS>{}, t + 1);
             };
-            if constexpr (!LATE && !(ABL & 4)) stage_next();
-            const u32x4* ws = s_w[(ABL & 4) ? 0 : (t & 1)][0] + lofs;
+            if constexpr (!LATE) stage_next();
+            const u32x4* ws = s_w[t & 1][0] + lofs;
             if constexpr (!A32 && SART_MF_XF_EARLY) {
                 // bf16: the step's W fragments are read once for all VT voxel tiles (the loop below re-read them per
                 // tile), all before the MFMAs (see k_mf_forward_b16_lds). Same accumulation order.
@@ -879,18 +859,10 @@ __global__ __launch_bounds__(256, (NG == 4 ? mf_bwd_min_waves<AT, VT>() : (std::
                     // six products: every piece pair of combined weight >= 2^-16 (hi, mid, lo of A and of W),
                     // smallest first into the accumulator
                     u32x4 fh[4], fm[4], fl[4];
-                    if constexpr ((ABL & 2) != 0) {
-#pragma unroll
-                        for (int p = 0; p < 4; ++p) {
-                            const u32x4 raw = {av[sl][vt][0][p], av[sl][vt][2][p], av[sl][vt][4][p], av[sl][vt][6][p]};
-                            fh[p] = raw, fm[p] = raw, fl[p] = raw;
-                        }
-                    } else {
-                        split_phase3<0>(av[sl][vt], fh[0], fm[0], fl[0]);
-                        split_phase3<1>(av[sl][vt], fh[1], fm[1], fl[1]);
-                        split_phase3<2>(av[sl][vt], fh[2], fm[2], fl[2]);
-                        split_phase3<3>(av[sl][vt], fh[3], fm[3], fl[3]);
-                    }
+                    split_phase3<0>(av[sl][vt], fh[0], fm[0], fl[0]);
+                    split_phase3<1>(av[sl][vt], fh[1], fm[1], fl[1]);
+                    split_phase3<2>(av[sl][vt], fh[2], fm[2], fl[2]);
+                    split_phase3<3>(av[sl][vt], fh[3], fm[3], fl[3]);
                     u32x4 wv[3][NG];
 #pragma unroll
                     for (int j = 0; j < NG; ++j)
@@ -903,12 +875,7 @@ __global__ __launch_bounds__(256, (NG == 4 ? mf_bwd_min_waves<AT, VT>() : (std::
 #pragma unroll
                         for (int j = 0; j < NG; ++j)
 #pragma unroll
-                            for (int p = 0; p < 4; ++p) {
-                                if constexpr ((ABL & 1) != 0)
-                                    acc[vt][p][j][0] += __uint_as_float((fa[p][0] ^ fa[p][3] ^ wv[pl][j][1]) & 0x3fffffu);
-                                else
-                                    acc[vt][p][j] = mfma_b16(fa[p], wv[pl][j], acc[vt][p][j]);
-                            }
+                            for (int p = 0; p < 4; ++p) acc[vt][p][j] = mfma_b16(fa[p], wv[pl][j], acc[vt][p][j]);
                     };
                     prod(fh, 2);
                     prod(fm, 1);
@@ -930,7 +897,6 @@ __global__ __launch_bounds__(256, (NG == 4 ? mf_bwd_min_waves<AT, VT>() : (std::
                     }
                 }
             }
-            if constexpr (ABL & 4) return;
             if constexpr (LATE) stage_next();
             __syncthreads();
         };
@@ -980,11 +946,7 @@ __device__ __forceinline__ void split_phase_h(const u32x4 (&v)[8], float s, u32x
 // MFMA chain runs over a whole split (a second register set spilled: 64 / 128 more VGPRs). Slots are lane-private
 // (no barrier, no atomics): 16 NG KiB per wave, 64 / 128 KiB per workgroup at 64 / 128 frames beside the 16 / 32 KiB
 // W stage (two workgroups per CU at 64 frames, one at 128: the occupancy the registers allow anyway). 0 disables
-// (A/B builds); the split count then has to shorten the chains instead (SART_MF_BP_BLOCKS).
-#ifndef SART_MF_BWD_FLUSH
-#define SART_MF_BWD_FLUSH 4
-#endif
-
+// (A/B builds; the default is set in engine/mf_plan.hpp, whose planner sizes the split count by it).
 // EW: W loaded a step ahead of A's batch (see k_mf_backproject_b16_lds); MW: waves per SIMD of the register budget
 template <int NG, int DEPTH, bool EW = false, int MW = 2>
 __global__ __launch_bounds__(256, MW) void k_mf_backproject_h16(const float* __restrict__ A, int64_t ld, int64_t nrows32,
@@ -1126,484 +1088,140 @@ __global__ __launch_bounds__(256, MW) void k_mf_backproject_h16(const float* __r
         }
 }
 
-// split128: the split-A forward and the f16-pair back-projection also take 128 frames (8 column groups)
-static void check_nf_b16(int nf, const char* what, bool split128 = false) {
-    if (nf == 128 && split128) return;
-    if (nf != 16 && nf != 32 && nf != 64)
-        throw std::runtime_error(std::string(what) + (split128 ? ": nf must be 16, 32, 64 or 128" : ": nf must be 16, 32 or 64"));
+// ------------------------------------------------------------------ launch: a table lookup per kernel signature
+// The tables are generated from the variant lists of engine/mf_variants.hpp, as is the planner's table of supported
+// keys (engine/mf_plan.cpp): a plan's key always has its entry here. All tunables are the planner's.
+namespace {
+typedef void (*FwdB16Fn)(const bf16_t*, int64_t, int64_t, int64_t, const bf16_t*, const bf16_t*, float*, FwdCols,
+                         const int*);
+typedef void (*FwdA32Fn)(const float*, int64_t, int64_t, int64_t, const bf16_t*, const bf16_t*, float*, FwdCols,
+                         const int*);
+typedef void (*BwdB16Fn)(const bf16_t*, int64_t, int64_t, const bf16_t*, const bf16_t*, int64_t, int64_t, float*,
+                         int64_t, int64_t, const int*);
+typedef void (*BwdX3Fn)(const float*, int64_t, int64_t, const bf16_t*, const bf16_t*, int64_t, int64_t, float*, int64_t,
+                        int64_t, const int*);
+typedef void (*BwdH16Fn)(const float*, int64_t, int64_t, const uint16_t*, const uint16_t*, int64_t, int64_t, float*,
+                         int64_t, int64_t, const float*, const float*, const int*);
+
+template <bool LDS, int NG, int DEPTH, int RT, int KB, bool AS, bool EX>
+constexpr FwdB16Fn fwd_b16_kernel() {
+    if constexpr (LDS) return k_mf_forward_b16_lds<NG, DEPTH, RT, KB, bf16_t, AS, EX>;
+    else return k_mf_forward_b16<NG, DEPTH, RT, KB>;
+}
+template <bool LDS, int NG, int DEPTH, int VT, bool EW>
+constexpr BwdB16Fn bwd_b16_kernel() {
+    if constexpr (LDS) return k_mf_backproject_b16_lds<NG, DEPTH, VT, bf16_t, EW>;
+    else return k_mf_backproject_b16<NG, DEPTH, VT>;
 }
 
-// Tunables (tools/probe_mf_b16.py): register-ring depth (SART_MF_DEPTH 1..3), forward tile (SART_MF_B16_FWD =
-// "RT,KB": 16-row tiles per wave and 32-voxel blocks per step) and back-projection voxel blocks per wave
-// (SART_MF_B16_VT 1 or 2). Defaults below from the probe at 64k x 64k (profiles/probe_r2_mf_b16.jsonl).
-static int env_int(const char* name, int dflt) {
-    const char* e = std::getenv(name);
-    return (e && *e) ? std::atoi(e) : dflt;
-}
-
-static int mf_b16_depth(bool forward, int nf) {
-    const int d = env_int("SART_MF_DEPTH", 0);
-    if (d >= 1 && d <= 3) return d;
-    (void)forward;
-    (void)nf;
-    return 3;  // profiles/probe_r2_mf_b16_bwd.jsonl
-}
-
-struct FwdTile {
-    int rt, kb;
-    bool lds = false;  // X shared through LDS (k_mf_forward_b16_lds)
-    bool as = false;   // A staged through LDS in full row segments (LDS kernel, 128-B rows: bf16 KB = 2, fp32)
+const MfVariant<FwdB16Fn> kFwdB16[] = {
+#define X(LDS, NG, D, RT, KB, AS, EX) \
+    {mf_key_fwd_b16(LDS, NG, D, RT, KB, AS, EX), fwd_b16_kernel<LDS, NG, D, RT, KB, AS, EX>()},
+    MF_FWD_B16_VARIANTS(X)
+#undef X
 };
-static FwdTile mf_b16_fwd_tile(int nf) {
-    const char* e = std::getenv("SART_MF_B16_FWD");
-    if (e && *e) {
-        // "RT,KB" or "RT,KB,lds"
-        FwdTile t{std::atoi(e), std::strchr(e, ',') ? std::atoi(std::strchr(e, ',') + 1) : 1};
-        t.lds = std::strstr(e, "lds") != nullptr;
-        t.as = std::strstr(e, "as") != nullptr;  // "RT,2,lds,as": A staged through LDS (KB = 2 only)
-        if ((t.rt == 2 || t.rt == 4 || t.rt == 8) && (t.kb == 1 || t.kb == 2)) return t;
-    }
-    // profiles/probe_r2_mf_b16_lds.jsonl, profiles/probe_r2_mf_as.jsonl (A staged: +9 % at 32 frames, a tie at 16 / 64)
-    if (nf == 32) return FwdTile{2, 2, true, true};
-    return nf == 16 ? FwdTile{2, 2, true} : FwdTile{4, 2, true};
+const MfVariant<FwdA32Fn> kFwdA32[] = {
+#define X(H16, NG, D, RT, KB, AS, EX) \
+    {mf_key_fwd_a32(H16, NG, D, RT, KB, AS, EX), k_mf_forward_b16_lds<NG, D, RT, KB, float, AS, EX, H16>},
+    MF_FWD_A32_VARIANTS(X)
+#undef X
+};
+const MfVariant<BwdB16Fn> kBwdB16[] = {
+#define X(LDS, NG, D, VT, EW) {mf_key_bwd_b16(LDS, NG, D, VT, EW), bwd_b16_kernel<LDS, NG, D, VT, EW>()},
+    MF_BWD_B16_VARIANTS(X)
+#undef X
+};
+const MfVariant<BwdX3Fn> kBwdX3[] = {
+#define X(NG, D, VT, EW) {mf_key_bwd_x3(NG, D, VT, EW), k_mf_backproject_b16_lds<NG, D, VT, float, EW>},
+    MF_BWD_X3_VARIANTS(X)
+#undef X
+};
+const MfVariant<BwdH16Fn> kBwdH16[] = {
+#define X(NG, D, EW, MW) {mf_key_bwd_h16(NG, D, EW, MW), k_mf_backproject_h16<NG, D, EW, MW>},
+    MF_BWD_H16_VARIANTS(X)
+#undef X
+};
+
+void check_plan(const MfKey& key, MfPath path, bool forward, const char* what) {
+    if (key.path != path || key.forward != forward)
+        throw std::runtime_error(std::string(what) + ": the plan was made for another path");
 }
 
-static int mf_b16_vt(int64_t ld, int nf) {
-    if (nf == 128) return 1;  // 8 column groups: one 64-voxel tile per wave
-    const int v = env_int("SART_MF_B16_VT", 0);
-    const int vt = (v == 1 || v == 2) ? v : 2;
-    return (vt == 2 && ld % 128 == 0) ? 2 : 1;
-}
-
-// W shared through LDS in the back-projection (k_mf_backproject_b16_lds): SART_MF_B16_VT = "VT,lds" / "VT,reg"
-static bool mf_b16_bwd_lds(int nf) {
-    const char* e = std::getenv("SART_MF_B16_VT");
-    if (e && std::strstr(e, "lds")) return true;
-    if (e && std::strstr(e, "reg")) return false;
-    (void)nf;
-    return true;
-}
-
-template <int NG, int DEPTH, int RT, int KB, typename AT>
-static void fwd_b16_t(FwdTile tl, dim3 grid, hipStream_t stream, const AT* A, int64_t ld, int64_t nrows,
-                      int64_t nrows_pad, const bf16_t* Xh, const bf16_t* Xl, float* Fout, FwdCols cps) {
-    constexpr bool A32 = std::is_same<AT, float>::value;
-    constexpr bool CAN_AS = A32 || KB == 2;  // full 128-B row segments per step
-    if constexpr (A32 && NG == 4 && DEPTH == 3 && RT == 2 && KB == 1) {
-        const int abl = env_int("SART_MF_ABL", 0);  // diagnostics only (tools/probe_mf_abl.py)
-        if (abl > 0 && tl.as) {
-            auto go = [&](auto k) {
-                hipLaunchKernelGGL((k_mf_forward_b16_lds<NG, DEPTH, RT, KB, AT, true, decltype(k)::value>), grid,
-                                   dim3(256), 0, stream, A, ld, nrows, nrows_pad, Xh, Xl, Fout, cps, g_mf_skip);
-            };
-            switch (abl & 7) {
-                case 1: go(std::integral_constant<int, 1>{}); break;
-                case 2: go(std::integral_constant<int, 2>{}); break;
-                case 3: go(std::integral_constant<int, 3>{}); break;
-                case 4: go(std::integral_constant<int, 4>{}); break;
-                case 5: go(std::integral_constant<int, 5>{}); break;
-                case 6: go(std::integral_constant<int, 6>{}); break;
-                default: go(std::integral_constant<int, 7>{}); break;
-            }
-            return;
-        }
-    }
-    // SART_MF_XEARLY=0 / 1: X loaded with A / a step earlier (A/B runs). Default: split-A only (+0.3 %; bf16 storage
-    // -2.7 %, profiles/ab_r4_mf_early_operands.jsonl)
-    const bool ex = env_int("SART_MF_XEARLY", A32 ? 1 : 0) != 0;
-    if constexpr (CAN_AS) {
-        if (tl.as) {
-            if (ex)
-                hipLaunchKernelGGL((k_mf_forward_b16_lds<NG, DEPTH, RT, KB, AT, true, 0, true>), grid, dim3(256), 0,
-                                   stream, A, ld, nrows, nrows_pad, Xh, Xl, Fout, cps, g_mf_skip);
-            else
-                hipLaunchKernelGGL((k_mf_forward_b16_lds<NG, DEPTH, RT, KB, AT, true>), grid, dim3(256), 0, stream, A,
-                                   ld, nrows, nrows_pad, Xh, Xl, Fout, cps, g_mf_skip);
-            return;
-        }
-    }
-    if ((A32 || tl.lds) && ex) {
-        hipLaunchKernelGGL((k_mf_forward_b16_lds<NG, DEPTH, RT, KB, AT, false, 0, true>), grid, dim3(256), 0, stream, A,
-                           ld, nrows, nrows_pad, Xh, Xl, Fout, cps, g_mf_skip);
-    } else if (A32 || tl.lds) {  // split-A: the LDS kernels only
-        hipLaunchKernelGGL((k_mf_forward_b16_lds<NG, DEPTH, RT, KB, AT>), grid, dim3(256), 0, stream, A, ld, nrows,
-                           nrows_pad, Xh, Xl, Fout, cps, g_mf_skip);
-    } else if constexpr (!A32) {
-        hipLaunchKernelGGL((k_mf_forward_b16<NG, DEPTH, RT, KB>), grid, dim3(256), 0, stream, A, ld, nrows, nrows_pad,
-                           Xh, Xl, Fout, cps, g_mf_skip);
-    }
-}
-
-template <int NG, int DEPTH, typename AT>
-static void fwd_b16_d(FwdTile tl, dim3 grid, hipStream_t stream, const AT* A, int64_t ld, int64_t nrows,
-                      int64_t nrows_pad, const bf16_t* Xh, const bf16_t* Xl, float* Fout, FwdCols cps) {
-    if (tl.rt == 2 && tl.kb == 2)
-        fwd_b16_t<NG, DEPTH, 2, 2>(tl, grid, stream, A, ld, nrows, nrows_pad, Xh, Xl, Fout, cps);
-    else if (tl.rt == 4 && tl.kb == 2)
-        fwd_b16_t<NG, DEPTH, 4, 2>(tl, grid, stream, A, ld, nrows, nrows_pad, Xh, Xl, Fout, cps);
-    else if (tl.rt == 2)
-        fwd_b16_t<NG, DEPTH, 2, 1>(tl, grid, stream, A, ld, nrows, nrows_pad, Xh, Xl, Fout, cps);
-    else if constexpr (!std::is_same<AT, float>::value) {
-        if (tl.rt == 8)
-            fwd_b16_t<NG, DEPTH, 8, 1>(tl, grid, stream, A, ld, nrows, nrows_pad, Xh, Xl, Fout, cps);
-        else
-            fwd_b16_t<NG, DEPTH, 4, 1>(tl, grid, stream, A, ld, nrows, nrows_pad, Xh, Xl, Fout, cps);
-    } else {
-        fwd_b16_t<NG, DEPTH, 4, 1>(tl, grid, stream, A, ld, nrows, nrows_pad, Xh, Xl, Fout, cps);
-    }
-}
-
-template <int NG, typename AT>
-static void fwd_b16(int depth, FwdTile tl, dim3 grid, hipStream_t stream, const AT* A, int64_t ld, int64_t nrows,
-                    int64_t nrows_pad, const bf16_t* Xh, const bf16_t* Xl, float* Fout, FwdCols cps) {
-    if constexpr (!std::is_same<AT, float>::value) {
-        if (depth == 1) {
-            fwd_b16_d<NG, 1>(tl, grid, stream, A, ld, nrows, nrows_pad, Xh, Xl, Fout, cps);
-            return;
-        }
-    }
-    if (depth <= 2)
-        fwd_b16_d<NG, 2>(tl, grid, stream, A, ld, nrows, nrows_pad, Xh, Xl, Fout, cps);
-    else
-        fwd_b16_d<NG, 3>(tl, grid, stream, A, ld, nrows, nrows_pad, Xh, Xl, Fout, cps);
-}
-
-// Split-A tunables (fp32 A on the bf16 matrix cores): SART_MF_X3_FWD = "RT,KB", SART_MF_X3_VT = VT (1 or 2),
-// SART_MF_X3_DEPTH (2 or 3). Twice the bytes of A per fragment as bf16 storage, so smaller register tiles.
-static FwdTile mf_x3_fwd_tile(int nf, int64_t ld) {
-    const char* e = std::getenv("SART_MF_X3_FWD");
-    if (e && *e) {
-        FwdTile t{std::atoi(e), std::strchr(e, ',') ? std::atoi(std::strchr(e, ',') + 1) : 1, true};
-        t.as = std::strstr(e, "as") != nullptr;  // "RT,KB,as": A staged through LDS
-        if ((t.rt == 2 || t.rt == 4) && (t.kb == 1 || t.kb == 2)) return t;
-    }
-    // profiles/probe_r2_mf_x3.jsonl, profiles/probe_r2_mf_as.jsonl; with blocked X planes (round 4,
-    // profiles/probe_r4_mf_x3_fwd_tiles_xblk.jsonl) 64 frames on rows of >= 128k columns take two 32-voxel blocks per
-    // step (16384 x 262144: 3.08 against 3.21 ms; 64k x 64k: 2.96 against 2.90, so narrower rows keep one)
-    // 32 frames take the A-staged tile too since its loads are non-temporal (+3.2 % at 64k x 64k,
-    // profiles/ab_r5_mf32_as.txt)
-    if (nf == 64 || nf == 32) return ld >= 131072 ? FwdTile{2, 2, true, true} : FwdTile{2, 1, true, true};
-    if (nf == 128) return FwdTile{2, 1, true, true};  // 128 frames: one 32-voxel block per step (registers)
-    return FwdTile{2, 2, true};
-}
-static int mf_x3_depth(bool forward) {
-    // the forward's ring: 2 steps ahead on blocked X planes (64k x 64k: 2.90 against 2.98 ms at 3, 16384 x 262144
-    // equal; profiles/probe_r4_mf_x3_fwd_tiles_xblk.jsonl)
-    (void)forward;
-    const int d = env_int("SART_MF_X3_DEPTH", 0);
-    return (d == 2 || d == 3) ? d : 2;
-}
-static int mf_x3_vt(int64_t ld) {
-    const int v = env_int("SART_MF_X3_VT", 0);
-    const int vt = (v == 1 || v == 2) ? v : 1;
-    return (vt == 2 && ld % 128 == 0) ? 2 : 1;
-}
-
-template <typename AT>
-static void launch_mf_forward_split(const AT* A, int64_t ld, int64_t nrows, int64_t nrows_pad, const bf16_t* Xh,
-                                    const bf16_t* Xl, float* Fout, int nsplit, int nf, hipStream_t stream,
-                                    bool xblk) {
-    constexpr bool A32 = std::is_same<AT, float>::value;
-    const char* what = A32 ? "mf_forward_x3" : "mf_forward_b16";
-    if (ld % 64 != 0) throw std::runtime_error(std::string(what) + ": ld must be a multiple of 64");
-    if (nsplit < 1) throw std::runtime_error(std::string(what) + ": nsplit must be >= 1");
-    check_nf_b16(nf, what, true);
-    if (nrows_pad % 32 != 0) throw std::runtime_error(std::string(what) + ": padded rows must be a multiple of 32");
-    FwdTile tl = A32 ? mf_x3_fwd_tile(nf, ld) : mf_b16_fwd_tile(nf);
-    if (nrows_pad % (16 * tl.rt) != 0) tl = FwdTile{2, 1, tl.lds, A32 && tl.as};  // a wave's rows inside the padding
-    // the 128-frame tilings (see below); bf16 storage stages A through LDS (+3.8 %, profiles/ab_r4_mfb128_variants.jsonl)
-    if (nf == 128) tl = FwdTile{2, A32 ? tl.kb : 2, true, true};
-    const FwdCols cps{((ld + nsplit - 1) / nsplit + 63) / 64 * 64, xblk ? 32 : ld, xblk ? 32 * (int64_t)nf : 32};
-    const int64_t rows_per_block = 64 * tl.rt;
-    const dim3 grid((unsigned)((nrows_pad + rows_per_block - 1) / rows_per_block), (unsigned)nsplit);
-    const int d = A32 ? mf_x3_depth(true) : mf_b16_depth(true, nf);
-    if constexpr (A32) {
-        if (nf == 128) {  // 8 column groups (64 accumulator registers at RT = 2): A staged, X early
-            auto run = [&](auto kern) {
-                hipLaunchKernelGGL(kern, grid, dim3(256), 0, stream, A, ld, nrows, nrows_pad, Xh, Xl, Fout, cps,
-                                   g_mf_skip);
-            };
-            if (tl.kb == 2 && d == 3) run(k_mf_forward_b16_lds<8, 3, 2, 2, float, true, 0, true>);
-            else if (tl.kb == 2) run(k_mf_forward_b16_lds<8, 2, 2, 2, float, true, 0, true>);
-            else if (d == 3) run(k_mf_forward_b16_lds<8, 3, 2, 1, float, true, 0, true>);
-            else run(k_mf_forward_b16_lds<8, 2, 2, 1, float, true, 0, true>);
-            check_launch("k_mf_forward_x3");
-            return;
-        }
-    }
-    if constexpr (!A32) {
-        if (nf == 128) {  // bf16 storage, 128 frames: 8 column groups, RT = 2, two 32-voxel blocks per step, X in LDS
-            auto run = [&](auto kern) {
-                hipLaunchKernelGGL(kern, grid, dim3(256), 0, stream, A, ld, nrows, nrows_pad, Xh, Xl, Fout, cps,
-                                   g_mf_skip);
-            };
-            if (tl.as && d >= 3) run(k_mf_forward_b16_lds<8, 3, 2, 2, bf16_t, true>);
-            else if (tl.as) run(k_mf_forward_b16_lds<8, 2, 2, 2, bf16_t, true>);
-            else if (d >= 3) run(k_mf_forward_b16_lds<8, 3, 2, 2, bf16_t>);
-            else run(k_mf_forward_b16_lds<8, 2, 2, 2, bf16_t>);
-            check_launch("k_mf_forward_b16");
-            return;
-        }
-    }
-    if (nf == 16)
-        fwd_b16<1>(d, tl, grid, stream, A, ld, nrows, nrows_pad, Xh, Xl, Fout, cps);
-    else if (nf == 32)
-        fwd_b16<2>(d, tl, grid, stream, A, ld, nrows, nrows_pad, Xh, Xl, Fout, cps);
-    else
-        fwd_b16<4>(d, tl, grid, stream, A, ld, nrows, nrows_pad, Xh, Xl, Fout, cps);
-    check_launch(A32 ? "k_mf_forward_x3" : "k_mf_forward_b16");
-}
-
-void launch_mf_forward_b16(const bf16_t* A, int64_t ld, int64_t nrows, int64_t nrows_pad, const bf16_t* Xh,
-                           const bf16_t* Xl, float* Fout, int nsplit, int nf, hipStream_t stream, bool xblk) {
-    launch_mf_forward_split(A, ld, nrows, nrows_pad, Xh, Xl, Fout, nsplit, nf, stream, xblk);
-}
-
-void launch_mf_forward_x3(const float* A, int64_t ld, int64_t nrows, int64_t nrows_pad, const bf16_t* Xh,
-                          const bf16_t* Xl, float* Fout, int nsplit, int nf, hipStream_t stream, bool xblk) {
-    launch_mf_forward_split(A, ld, nrows, nrows_pad, Xh, Xl, Fout, nsplit, nf, stream, xblk);
-}
-
-// The f16-pair split-A forward (H16; default for fp32 shards at 32 / 64 / 128 frames): the x3 tilings with RT = 2 and
-// a ring two steps deep, X loaded early; planes from launch_mf_split_x16 with perm (and blocked when xblk).
-template <int NG>
-static void fwd_h16_ng(const FwdTile& tl, dim3 grid, hipStream_t stream, const float* A, int64_t ld, int64_t nrows,
-                       int64_t nrows_pad, const bf16_t* X1, const bf16_t* X2, float* Fout, FwdCols cps) {
-    auto run = [&](auto kern) {
-        hipLaunchKernelGGL(kern, grid, dim3(256), 0, stream, A, ld, nrows, nrows_pad, X1, X2, Fout, cps, g_mf_skip);
-    };
-    // SART_MF_H16_FDEPTH=3: a register ring three steps deep for the A-staged tilings (A/B runs)
-    if (tl.as && env_int("SART_MF_H16_FDEPTH", 2) == 3) {
-        if (tl.kb == 2) run(k_mf_forward_b16_lds<NG, 3, 2, 2, float, true, 0, true, true>);
-        else run(k_mf_forward_b16_lds<NG, 3, 2, 1, float, true, 0, true, true>);
-        return;
-    }
-    if (tl.kb == 2 && tl.as) run(k_mf_forward_b16_lds<NG, 2, 2, 2, float, true, 0, true, true>);
-    else if (tl.kb == 2) run(k_mf_forward_b16_lds<NG, 2, 2, 2, float, false, 0, true, true>);
-    else if (tl.as) run(k_mf_forward_b16_lds<NG, 2, 2, 1, float, true, 0, true, true>);
-    else run(k_mf_forward_b16_lds<NG, 2, 2, 1, float, false, 0, true, true>);
-}
-
-void launch_mf_forward_h16(const float* A, int64_t ld, int64_t nrows, int64_t nrows_pad, const uint16_t* X1,
-                           const uint16_t* X2, float* Fout, int nsplit, int nf, hipStream_t stream, bool xblk,
-                           const float* rsc, const float* xinv) {
-    const char* what = "mf_forward_h16";
-    if (ld % 64 != 0) throw std::runtime_error(std::string(what) + ": ld must be a multiple of 64");
-    if (nsplit < 1) throw std::runtime_error(std::string(what) + ": nsplit must be >= 1");
-    check_nf_b16(nf, what, true);
-    if (nrows_pad % 64 != 0) throw std::runtime_error(std::string(what) + ": padded rows must be a multiple of 64");
-    if (!rsc || !xinv) throw std::runtime_error(std::string(what) + ": row scales and frame scales required");
-    FwdTile tl = mf_x3_fwd_tile(nf, ld);
-    if (nf == 128) tl.as = true;
-    FwdCols cps{((ld + nsplit - 1) / nsplit + 63) / 64 * 64, xblk ? 32 : ld, xblk ? 32 * (int64_t)nf : 32};
+template <typename Fn, size_t N, typename AT, typename XT>
+void forward_split(const MfVariant<Fn> (&table)[N], const char* what, const MfFwdPlan& p, const AT* A, int64_t nrows,
+                   const XT* Xh, const XT* Xl, float* Fout, hipStream_t stream, bool xblk, const float* rsc,
+                   const float* xinv) {
+    FwdCols cps{p.cps, xblk ? 32 : p.ld, xblk ? 32 * (int64_t)p.nf : 32};
     cps.rsc = rsc;
     cps.xinv = xinv;
-    const dim3 grid((unsigned)((nrows_pad + 127) / 128), (unsigned)nsplit);  // 4 waves x 32 rows per workgroup
-    const bf16_t* x1 = reinterpret_cast<const bf16_t*>(X1);
-    const bf16_t* x2 = reinterpret_cast<const bf16_t*>(X2);
-    if (nf == 16) fwd_h16_ng<1>(tl, grid, stream, A, ld, nrows, nrows_pad, x1, x2, Fout, cps);
-    else if (nf == 32) fwd_h16_ng<2>(tl, grid, stream, A, ld, nrows, nrows_pad, x1, x2, Fout, cps);
-    else if (nf == 64) fwd_h16_ng<4>(tl, grid, stream, A, ld, nrows, nrows_pad, x1, x2, Fout, cps);
-    else fwd_h16_ng<8>(tl, grid, stream, A, ld, nrows, nrows_pad, x1, x2, Fout, cps);
-    check_launch("k_mf_forward_h16");
+    hipLaunchKernelGGL(mf_variant(table, p.key, what), dim3(p.grid_x, (unsigned)p.nsplit), dim3(256), 0, stream, A,
+                       p.ld, nrows, p.nrows_pad, reinterpret_cast<const bf16_t*>(Xh),
+                       reinterpret_cast<const bf16_t*>(Xl), Fout, cps, g_mf_skip);
+    check_launch(what);
 }
 
-// Split-K of the bf16 / split-A back-projection: ~1024 workgroups (4 waves x 64 VT voxels each), >= 64 rows per
-// split.
-int mf_backproject_b16_num_splits(int64_t ld, int64_t nrows, bool a32) {
-    const int64_t nblk = (ld / (64 * (a32 ? mf_x3_vt(ld) : mf_b16_vt(ld, 0))) + 3) / 4;
-    // bf16 storage: ~512 (fewer partial slices for k_mf_collect: +1.3 % with 512-block forwards at 64 frames,
-    // profiles/ab_r4_mf_split_blocks_low.jsonl); split-A ~1024 (256: -5 %)
-    // x 4 in round 6 (split-A 4096, bf16 storage 2048): each split's rows are one fp32 MFMA accumulation chain, the
-    // larger share of the engine's error against the fp32 two-pass kernels at 64k x 64k (16k-row chains;
-    // profiles/parity_r6_64k_mf_chains.jsonl)
-    // (split-A with the LDS two-level sums of k_mf_backproject_h16: back to ~1024, chains of 12 steps)
-    const int64_t target = env_int("SART_MF_BP_BLOCKS", a32 ? (SART_MF_BWD_FLUSH > 0 ? 1024 : 4096) : 2048);
-    int64_t s = (target + nblk - 1) / nblk;
-    const int64_t smax = (nrows + 63) / 64;
-    if (s > smax) s = smax;
-    if (s < 1) s = 1;
-    return (int)s;
-}
-
-int mf_backproject_b16_vox_align(int64_t ld, bool a32) { return 64 * (a32 ? mf_x3_vt(ld) : mf_b16_vt(ld, 0)); }
-
-template <int NG, int DEPTH, typename AT>
-static void bwd_b16_d(int vt, dim3 grid, hipStream_t stream, const AT* A, int64_t ld, int64_t nrows32,
-                      const bf16_t* Wh, const bf16_t* Wl, int64_t ldw, int64_t rps, float* partial, int64_t vb0,
-                      int64_t vend) {
-    if constexpr (std::is_same<AT, float>::value && NG == 4 && DEPTH == 2) {
-        const int abl = env_int("SART_MF_ABL", 0);  // diagnostics only (tools/probe_mf_abl.py; read per launch)
-        if (abl > 0 && vt == 1) {
-            auto go = [&](auto k) {
-                hipLaunchKernelGGL((k_mf_backproject_b16_lds<NG, DEPTH, 1, AT, decltype(k)::value>), grid, dim3(256), 0,
-                                   stream, A, ld, nrows32, Wh, Wl, ldw, rps, partial, vb0, vend, g_mf_skip);
-            };
-            switch (abl & 7) {
-                case 1: go(std::integral_constant<int, 1>{}); break;
-                case 2: go(std::integral_constant<int, 2>{}); break;
-                case 3: go(std::integral_constant<int, 3>{}); break;
-                case 4: go(std::integral_constant<int, 4>{}); break;
-                case 5: go(std::integral_constant<int, 5>{}); break;
-                case 6: go(std::integral_constant<int, 6>{}); break;
-                default: go(std::integral_constant<int, 7>{}); break;
-            }
-            return;
-        }
-    }
-    if (std::is_same<AT, float>::value || mf_b16_bwd_lds(16 * NG)) {
-        // SART_MF_WEARLY=0 / 1: W loaded in one batch with A / one step earlier (A/B runs; read per launch). Default
-        // on for bf16 storage (+0.9 %); off for split-A, whose two-waves-per-SIMD budget spills 40 VGPRs with the extra
-        // W slot (-12 %, profiles/ab_r4_mf_early_operands.jsonl)
-        if (env_int("SART_MF_WEARLY", std::is_same<AT, float>::value ? 0 : 1) != 0) {
-            if (vt == 2)
-                hipLaunchKernelGGL((k_mf_backproject_b16_lds<NG, DEPTH, 2, AT, 0, true>), grid, dim3(256), 0, stream, A,
-                                   ld, nrows32, Wh, Wl, ldw, rps, partial, vb0, vend, g_mf_skip);
-            else
-                hipLaunchKernelGGL((k_mf_backproject_b16_lds<NG, DEPTH, 1, AT, 0, true>), grid, dim3(256), 0, stream, A,
-                                   ld, nrows32, Wh, Wl, ldw, rps, partial, vb0, vend, g_mf_skip);
-            return;
-        }
-        if (vt == 2)
-            hipLaunchKernelGGL((k_mf_backproject_b16_lds<NG, DEPTH, 2, AT>), grid, dim3(256), 0, stream, A, ld,
-                               nrows32, Wh, Wl, ldw, rps, partial, vb0, vend, g_mf_skip);
-        else
-            hipLaunchKernelGGL((k_mf_backproject_b16_lds<NG, DEPTH, 1, AT>), grid, dim3(256), 0, stream, A, ld,
-                               nrows32, Wh, Wl, ldw, rps, partial, vb0, vend, g_mf_skip);
-        return;
-    }
-    if constexpr (!std::is_same<AT, float>::value) {
-        if (vt == 2)
-            hipLaunchKernelGGL((k_mf_backproject_b16<NG, DEPTH, 2>), grid, dim3(256), 0, stream, A, ld, nrows32, Wh,
-                               Wl, ldw, rps, partial, vb0, vend, g_mf_skip);
-        else
-            hipLaunchKernelGGL((k_mf_backproject_b16<NG, DEPTH, 1>), grid, dim3(256), 0, stream, A, ld, nrows32, Wh,
-                               Wl, ldw, rps, partial, vb0, vend, g_mf_skip);
-    }
-}
-
-template <int NG, typename AT>
-static void bwd_b16(int depth, int vt, dim3 grid, hipStream_t stream, const AT* A, int64_t ld, int64_t nrows32,
-                    const bf16_t* Wh, const bf16_t* Wl, int64_t ldw, int64_t rps, float* partial, int64_t vb0,
-                    int64_t vend) {
-    if constexpr (!std::is_same<AT, float>::value) {
-        if (depth == 1) {
-            bwd_b16_d<NG, 1>(vt, grid, stream, A, ld, nrows32, Wh, Wl, ldw, rps, partial, vb0, vend);
-            return;
-        }
-    }
-    if (depth <= 2)
-        bwd_b16_d<NG, 2>(vt, grid, stream, A, ld, nrows32, Wh, Wl, ldw, rps, partial, vb0, vend);
-    else
-        bwd_b16_d<NG, 3>(vt, grid, stream, A, ld, nrows32, Wh, Wl, ldw, rps, partial, vb0, vend);
-}
-
-template <typename AT>
-static void launch_mf_backproject_split(const AT* A, int64_t ld, int64_t nrows, const bf16_t* Wh, const bf16_t* Wl,
-                                        int64_t ldw, int nsplit, float* partial, int nf, hipStream_t stream,
-                                        int64_t v0, int64_t v1) {
-    constexpr bool A32 = std::is_same<AT, float>::value;
-    const std::string what = A32 ? "mf_backproject_x3" : "mf_backproject_b16";
-    if (ld % 64 != 0) throw std::runtime_error(what + ": ld must be a multiple of 64");
-    check_nf_b16(nf, what.c_str(), !A32);  // 128 frames: bf16 storage (split-A takes launch_mf_backproject_h16)
-    const int64_t nrows32 = (nrows + 31) / 32 * 32;
-    if (ldw < nrows32 || ldw % 8 != 0)
+// the wave tiles [vw0, vw0 + nvw) of a voxel range aligned to the kernel's tile
+int64_t wave_tiles(const MfBwdPlan& p, int64_t ldw, int64_t v0, int64_t& v1, const std::string& what) {
+    if (ldw < (p.nrows + 31) / 32 * 32 || ldw % 8 != 0)
         throw std::runtime_error(what + ": W planes must hold the rows rounded up to 32 (ldw % 8 == 0)");
-    if (v1 < 0) v1 = ld;
-    const int vt = A32 ? mf_x3_vt(ld) : mf_b16_vt(ld, nf);
-    const int64_t align = 64 * vt;
-    if (v0 < 0 || v1 > ld || v0 >= v1 || v0 % align != 0 || v1 % align != 0)
+    if (v1 < 0) v1 = p.ld;
+    const int64_t tile = 64 * p.key.tile;
+    if (v0 < 0 || v1 > p.ld || v0 >= v1 || v0 % tile != 0 || v1 % tile != 0)
         throw std::runtime_error(what + ": voxel range must be aligned to the wave's voxel tile");
-    if (nsplit < 1) throw std::runtime_error(what + ": nsplit must be >= 1");
-    const int64_t rps = ((nrows32 + nsplit - 1) / nsplit + 31) / 32 * 32;
-    const int64_t vw0 = v0 / align, nvw = (v1 - v0) / align;  // wave tiles
-    const dim3 grid((unsigned)((nvw + 3) / 4), (unsigned)nsplit);
-    const int d = A32 ? mf_x3_depth(false) : mf_b16_depth(false, nf);
-    if constexpr (!A32) {
-        if (nf == 128) {  // 8 column groups, one 64-voxel tile per wave (VT = 1), W in LDS, W loaded early
-            auto run = [&](auto kern) {
-                hipLaunchKernelGGL(kern, grid, dim3(256), 0, stream, A, ld, nrows32, Wh, Wl, ldw, rps, partial, vw0, v1,
-                                   g_mf_skip);
-            };
-            if (d >= 3) run(k_mf_backproject_b16_lds<8, 3, 1, bf16_t, 0, true>);
-            else run(k_mf_backproject_b16_lds<8, 2, 1, bf16_t, 0, true>);
-            check_launch("k_mf_backproject_b16");
-            return;
-        }
-    }
-    if (nf == 16)
-        bwd_b16<1>(d, vt, grid, stream, A, ld, nrows32, Wh, Wl, ldw, rps, partial, vw0, v1);
-    else if (nf == 32)
-        bwd_b16<2>(d, vt, grid, stream, A, ld, nrows32, Wh, Wl, ldw, rps, partial, vw0, v1);
-    else
-        bwd_b16<4>(d, vt, grid, stream, A, ld, nrows32, Wh, Wl, ldw, rps, partial, vw0, v1);
-    check_launch(A32 ? "k_mf_backproject_x3" : "k_mf_backproject_b16");
+    return v0 / tile;
+}
+}  // namespace
+
+void launch_mf_forward_b16(const MfFwdPlan& p, const bf16_t* A, int64_t nrows, const bf16_t* Xh, const bf16_t* Xl,
+                           float* Fout, hipStream_t stream, bool xblk) {
+    check_plan(p.key, MfPath::b16, true, "mf_forward_b16");
+    forward_split(kFwdB16, "k_mf_forward_b16", p, A, nrows, Xh, Xl, Fout, stream, xblk, nullptr, nullptr);
 }
 
-void launch_mf_backproject_b16(const bf16_t* A, int64_t ld, int64_t nrows, const bf16_t* Wh, const bf16_t* Wl,
-                               int64_t ldw, int nsplit, float* partial, int nf, hipStream_t stream, int64_t v0,
-                               int64_t v1) {
-    launch_mf_backproject_split(A, ld, nrows, Wh, Wl, ldw, nsplit, partial, nf, stream, v0, v1);
+void launch_mf_forward_x3(const MfFwdPlan& p, const float* A, int64_t nrows, const bf16_t* Xh, const bf16_t* Xl,
+                          float* Fout, hipStream_t stream, bool xblk) {
+    check_plan(p.key, MfPath::x3, true, "mf_forward_x3");
+    forward_split(kFwdA32, "k_mf_forward_x3", p, A, nrows, Xh, Xl, Fout, stream, xblk, nullptr, nullptr);
 }
 
-void launch_mf_backproject_h16(const float* A, int64_t ld, int64_t nrows, const uint16_t* W1, const uint16_t* W2,
-                               int64_t ldw, int nsplit, float* partial, int nf, hipStream_t stream, int64_t v0,
-                               int64_t v1, const float* csc, const float* inv_scale) {
-    const std::string what = "mf_backproject_h16";
-    if (!csc || !inv_scale) throw std::runtime_error(what + ": column scales and frame scales required");
-    if (ld % 64 != 0) throw std::runtime_error(what + ": ld must be a multiple of 64");
-    check_nf_b16(nf, what.c_str(), true);
-    const int64_t nrows32 = (nrows + 31) / 32 * 32;
-    if (ldw < nrows32 || ldw % 8 != 0)
-        throw std::runtime_error(what + ": W planes must hold the rows rounded up to 32 (ldw % 8 == 0)");
-    if (v1 < 0) v1 = ld;
-    if (v0 < 0 || v1 > ld || v0 >= v1 || v0 % 64 != 0 || v1 % 64 != 0)
-        throw std::runtime_error(what + ": voxel range must be aligned to 64");
-    if (nsplit < 1) throw std::runtime_error(what + ": nsplit must be >= 1");
-    const int64_t rps = ((nrows32 + nsplit - 1) / nsplit + 31) / 32 * 32;
-    const int64_t vw0 = v0 / 64, nvw = (v1 - v0) / 64;
-    const dim3 grid((unsigned)((nvw + 3) / 4), (unsigned)nsplit);
-    const int d = mf_x3_depth(false);
-    // SART_MF_H16 (A/B runs): "ew" early W loads, "w1" one wave per SIMD (512 registers), "ew,w1"
-    const char* hv = std::getenv("SART_MF_H16");
-    const bool ew = hv && std::strstr(hv, "ew"), w1 = hv && std::strstr(hv, "w1");
-    auto go = [&](auto ng) {
-        constexpr int NG = decltype(ng)::value;
-        auto run = [&](auto k) {
-            hipLaunchKernelGGL(k, grid, dim3(256), 0, stream, A, ld, nrows32, W1, W2, ldw, rps, partial, vw0, v1,
-                               csc, inv_scale, g_mf_skip);
-        };
-        if (w1 && ew && d == 3) run(k_mf_backproject_h16<NG, 3, true, 1>);
-        else if (w1 && d == 3) run(k_mf_backproject_h16<NG, 3, false, 1>);
-        else if (w1 && ew) run(k_mf_backproject_h16<NG, 2, true, 1>);
-        else if (w1) run(k_mf_backproject_h16<NG, 2, false, 1>);
-        else if (ew) run(k_mf_backproject_h16<NG, 2, true, 2>);
-        else if (d == 3) run(k_mf_backproject_h16<NG, 3>);
-        else run(k_mf_backproject_h16<NG, 2>);
-    };
-    if (nf == 16)
-        go(std::integral_constant<int, 1>{});
-    else if (nf == 32)
-        go(std::integral_constant<int, 2>{});
-    else if (nf == 64)
-        go(std::integral_constant<int, 4>{});
-    else {  // 128 frames: 8 column groups, one wave per SIMD (128 accumulator registers)
-        auto run = [&](auto kern) {
-            hipLaunchKernelGGL(kern, grid, dim3(256), 0, stream, A, ld, nrows32, W1, W2, ldw, rps, partial, vw0, v1,
-                               csc, inv_scale, g_mf_skip);
-        };
-        if (ew && d == 3) run(k_mf_backproject_h16<8, 3, true, 1>);
-        else if (ew) run(k_mf_backproject_h16<8, 2, true, 1>);
-        else if (d == 3) run(k_mf_backproject_h16<8, 3, false, 1>);
-        else run(k_mf_backproject_h16<8, 2, false, 1>);
-    }
+// The f16-pair split-A forward: planes from launch_mf_split_x16 with perm (and blocked when xblk).
+void launch_mf_forward_h16(const MfFwdPlan& p, const float* A, int64_t nrows, const uint16_t* X1, const uint16_t* X2,
+                           float* Fout, hipStream_t stream, bool xblk, const float* rsc, const float* xinv) {
+    check_plan(p.key, MfPath::h16, true, "mf_forward_h16");
+    if (!rsc || !xinv) throw std::runtime_error("mf_forward_h16: row scales and frame scales required");
+    forward_split(kFwdA32, "k_mf_forward_h16", p, A, nrows, X1, X2, Fout, stream, xblk, rsc, xinv);
+}
+
+void launch_mf_backproject_b16(const MfBwdPlan& p, const bf16_t* A, const bf16_t* Wh, const bf16_t* Wl, int64_t ldw,
+                               float* partial, hipStream_t stream, int64_t v0, int64_t v1) {
+    check_plan(p.key, MfPath::b16, false, "mf_backproject_b16");
+    const int64_t vw0 = wave_tiles(p, ldw, v0, v1, "mf_backproject_b16");
+    hipLaunchKernelGGL(mf_variant(kBwdB16, p.key, "mf_backproject_b16"), dim3(p.grid_x(v0, v1), (unsigned)p.nsplit),
+                       dim3(256), 0, stream, A, p.ld, (p.nrows + 31) / 32 * 32, Wh, Wl, ldw, p.rps, partial, vw0, v1,
+                       g_mf_skip);
+    check_launch("k_mf_backproject_b16");
+}
+
+void launch_mf_backproject_x3(const MfBwdPlan& p, const float* A, const bf16_t* Wh, const bf16_t* Wl, int64_t ldw,
+                              float* partial, hipStream_t stream, int64_t v0, int64_t v1) {
+    check_plan(p.key, MfPath::x3, false, "mf_backproject_x3");
+    const int64_t vw0 = wave_tiles(p, ldw, v0, v1, "mf_backproject_x3");
+    hipLaunchKernelGGL(mf_variant(kBwdX3, p.key, "mf_backproject_x3"), dim3(p.grid_x(v0, v1), (unsigned)p.nsplit),
+                       dim3(256), 0, stream, A, p.ld, (p.nrows + 31) / 32 * 32, Wh, Wl, ldw, p.rps, partial, vw0, v1,
+                       g_mf_skip);
+    check_launch("k_mf_backproject_x3");
+}
+
+void launch_mf_backproject_h16(const MfBwdPlan& p, const float* A, const uint16_t* W1, const uint16_t* W2, int64_t ldw,
+                               float* partial, hipStream_t stream, int64_t v0, int64_t v1, const float* csc,
+                               const float* inv_scale) {
+    check_plan(p.key, MfPath::h16, false, "mf_backproject_h16");
+    if (!csc || !inv_scale) throw std::runtime_error("mf_backproject_h16: column scales and frame scales required");
+    const int64_t vw0 = wave_tiles(p, ldw, v0, v1, "mf_backproject_h16");
+    hipLaunchKernelGGL(mf_variant(kBwdH16, p.key, "mf_backproject_h16"), dim3(p.grid_x(v0, v1), (unsigned)p.nsplit),
+                       dim3(256), 0, stream, A, p.ld, (p.nrows + 31) / 32 * 32, W1, W2, ldw, p.rps, partial, vw0, v1, csc,
+                       inv_scale, g_mf_skip);
     check_launch("k_mf_backproject_h16");
-}
-
-void launch_mf_backproject_x3(const float* A, int64_t ld, int64_t nrows, const bf16_t* Wh, const bf16_t* Wl,
-                              int64_t ldw, int nsplit, float* partial, int nf, hipStream_t stream, int64_t v0,
-                              int64_t v1) {
-    launch_mf_backproject_split(A, ld, nrows, Wh, Wl, ldw, nsplit, partial, nf, stream, v0, v1);
 }
 
 }  // namespace sart

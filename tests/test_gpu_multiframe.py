@@ -250,3 +250,50 @@ def test_final_sweep_skips_backprojection_bitwise(monkeypatch, log, tol):
         assert np.array_equal(a.solution, b.solution)
     if tol == 0.0:  # fixed iteration count: every frame reaches the final-sweep decision
         assert all(r.iterations == 12 for r in out["0"])
+
+
+@pytest.mark.parametrize("storage,batch,split_a", [("bf16", 32, None), ("fp32", 64, True)])
+def test_engine_plans_once(monkeypatch, storage, batch, split_a):
+    """The engine takes its launch plans (kernel variants, split counts, chunk alignment) at construction: tile and
+    split-count knobs set in the process afterwards change nothing. Six runs of 3 sweeps each on one engine, every run
+    started from frame 0's previous iterate, the knobs set after the third: all six iterates equal, bit for bit, those
+    of an engine that never saw the knobs. 2048 columns make VT = 2 the bf16 default (a tile re-derived per launch
+    would change the kernel and the partial slices); 1000 rows exercise the padded tail."""
+    from mpi_cuda_sartsolver_amd.models.multiframe import MultiFrameSARTSolver
+    from mpi_cuda_sartsolver_amd.models.rtm import DenseRTM
+    from mpi_cuda_sartsolver_amd.models.sart import SolverParams
+
+    knobs = {"SART_MF_B16_VT": "1", "SART_MF_X3_VT": "2", "SART_MF_X3_FWD": "4,2", "SART_MF_BP_BLOCKS": "64"}
+    for name in knobs:
+        monkeypatch.delenv(name, raising=False)
+    dev = torch.device("cuda", 0)
+    rng = np.random.default_rng(batch)
+    P, V = 1000, 2048
+    A = rng.random((P, V), dtype=np.float32)
+    rtm = DenseRTM.from_dense(A, device=dev, storage=storage)
+    G = (rng.random((batch, V)) + 0.05) @ A.T.astype(np.float64)
+
+    def engine():
+        s = MultiFrameSARTSolver(rtm, None, None, SolverParams(max_iterations=3, conv_tolerance=0.0), batch=batch,
+                                 allow_zero_tolerance=True, split_a=split_a)
+        assert s.batch_width == batch and s.split_a == bool(split_a)
+        return s
+
+    def run(s, x0):
+        return np.stack([r.solution for r in s.solve_batch(G, x0=x0)])
+
+    ref, x0 = [], None
+    s = engine()
+    for _ in range(6):
+        ref.append(run(s, x0))
+        x0 = ref[-1][0]
+    del s
+    s, x0 = engine(), None
+    for i in range(6):
+        if i == 3:
+            for name, val in knobs.items():
+                monkeypatch.setenv(name, val)
+        x = run(s, x0)
+        assert np.array_equal(x, ref[i]), i
+        x0 = x[0]
+    assert not np.array_equal(ref[0], ref[5])

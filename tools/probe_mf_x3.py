@@ -24,9 +24,6 @@ def main():
     m = DenseRTM.synthetic(P, V, 0, seed=1, device=dev)
     nbytes = m.nbytes
     nfs = [int(v) for v in os.environ.get("PROBE_NF", "16,32,64").split(",")]
-    fwd_tiles = os.environ.get("PROBE_FWD", "2,1;4,1;2,2;4,2").split(";")
-    vts = os.environ.get("PROBE_VT", "1;2").split(";")
-    depths = [int(v) for v in os.environ.get("PROBE_DEPTH", "2,3").split(",")]
 
     def emit(op, nf, med, **kw):
         print(json.dumps(dict(op=op, nf=nf, P=P, V=V, ms=round(med, 4), GBps=round(nbytes / med / 1e6, 1),
@@ -52,22 +49,22 @@ def main():
             med, _ = timeit(lambda: k.mf_backproject(m.A.data_ptr(), m.ld, P, W.data_ptr(), ns, part.data_ptr(), s,
                                                      nf), reps=5)
             emit("mf_backproject_fp32", nf, med, nsplit=ns)
-        for depth in depths:
-            os.environ["SART_MF_X3_DEPTH"] = str(depth)
-            for tile in fwd_tiles:
-                os.environ["SART_MF_X3_FWD"] = tile
-                med, _ = timeit(lambda: k.mf_forward_x3(m.A.data_ptr(), m.ld, P, m.nrows_pad, Xh.data_ptr(),
-                                                        Xl.data_ptr(), Fo.data_ptr(), nsf, s, nf), reps=5)
-                emit("mf_forward_x3", nf, med, depth=depth, tile=tile, nsplit=nsf)
-            for vt in vts:
-                os.environ["SART_MF_X3_VT"] = vt
-                ns = k.mf_backproject_b16_num_splits(m.ld, P, True)
-                assert ns <= 64
-                med, _ = timeit(lambda: k.mf_backproject_x3(m.A.data_ptr(), m.ld, P, Wh.data_ptr(), Wl.data_ptr(),
-                                                            m.nrows_pad, ns, part.data_ptr(), s, nf), reps=5)
-                emit("mf_backproject_x3", nf, med, depth=depth, vt=vt, nsplit=ns)
-        for key in ("SART_MF_X3_DEPTH", "SART_MF_X3_FWD", "SART_MF_X3_VT"):
-            os.environ.pop(key, None)
+        for forward in (True, False):
+            for var in k.mf_variants("x3", nf, forward):  # the launch table's keys, each with its knob setting
+                env = var.pop("env")
+                os.environ.update(env)
+                if forward:
+                    med, _ = timeit(lambda: k.mf_forward_x3(m.A.data_ptr(), m.ld, P, m.nrows_pad, Xh.data_ptr(),
+                                                            Xl.data_ptr(), Fo.data_ptr(), nsf, s, nf), reps=5)
+                    emit("mf_forward_x3", nf, med, nsplit=nsf, env=env, **var)
+                else:
+                    ns = k.mf_backproject_b16_num_splits(m.ld, P, True)
+                    assert ns <= 64
+                    med, _ = timeit(lambda: k.mf_backproject_x3(m.A.data_ptr(), m.ld, P, Wh.data_ptr(), Wl.data_ptr(),
+                                                                m.nrows_pad, ns, part.data_ptr(), s, nf), reps=5)
+                    emit("mf_backproject_x3", nf, med, nsplit=ns, env=env, **var)
+                for key in env:
+                    os.environ.pop(key, None)
         del X, Xh, Xl, Fo, W, Wh, Wl, part
         torch.cuda.empty_cache()
 
