@@ -173,6 +173,12 @@ static void bind_engine(py::module_& m) {
         .def_readwrite("use_graph", &sart::EngineConfig::use_graph)
         .def_readwrite("time_collectives", &sart::EngineConfig::time_collectives)
         .def_readwrite("rtm_bf16", &sart::EngineConfig::rtm_bf16)
+        // row-scaled f16 storage: row_scale is the device pointer of the shard's scale array ([nrows_pad] scales,
+        // then [nrows_pad] inverses; the caller keeps it alive with the engine)
+        .def_readwrite("rtm_f16", &sart::EngineConfig::rtm_f16)
+        .def_property("row_scale",
+                      [](const sart::EngineConfig& c) { return reinterpret_cast<uintptr_t>(c.row_scale); },
+                      [](sart::EngineConfig& c, uintptr_t p) { c.row_scale = P<const float>(p); })
         .def_readwrite("mf_split_a", &sart::EngineConfig::mf_split_a)
         .def_readwrite("fault_inject", &sart::EngineConfig::fault_inject)
         .def_readwrite("fault_nan_sweep", &sart::EngineConfig::fault_nan_sweep)
@@ -392,8 +398,13 @@ PYBIND11_MODULE(_sart_hip, m) {
     // bf16: A holds bf16 bit patterns (opt-in storage precision)
     m.def("forward", [](int epi, uintptr_t A, int64_t ld, int64_t nrows, int64_t nrows_pad, uintptr_t x,
                         uintptr_t ghat, uintptr_t arow, uintptr_t out_f, uintptr_t out_w, uintptr_t Fpart,
-                        uintptr_t st, uintptr_t stream, bool bf16) {
-        if (bf16)
+                        uintptr_t st, uintptr_t stream, bool bf16, bool f16, uintptr_t rinv) {
+        if (f16 && bf16) throw std::runtime_error("forward: bf16 and f16 are exclusive");
+        if (f16)  // row-scaled f16 bits; rinv: the rows' inverse scales
+            sart::launch_forward(epi, P<const sart::f16s_t>(A), ld, nrows, nrows_pad, P<const float>(x),
+                                 P<const float>(ghat), P<const float>(arow), P<float>(out_f), P<float>(out_w),
+                                 P<double>(Fpart), P<const sart::SartState>(st), S(stream), P<const float>(rinv));
+        else if (bf16)
             sart::launch_forward(epi, P<const sart::bf16_t>(A), ld, nrows, nrows_pad, P<const float>(x),
                                  P<const float>(ghat), P<const float>(arow), P<float>(out_f), P<float>(out_w),
                                  P<double>(Fpart), P<const sart::SartState>(st), S(stream));
@@ -403,33 +414,58 @@ PYBIND11_MODULE(_sart_hip, m) {
                                  P<const sart::SartState>(st), S(stream));
     }, py::arg("epi"), py::arg("A"), py::arg("ld"), py::arg("nrows"), py::arg("nrows_pad"), py::arg("x"),
        py::arg("ghat"), py::arg("arow"), py::arg("out_f"), py::arg("out_w"), py::arg("Fpart"), py::arg("st"),
-       py::arg("stream"), py::arg("bf16") = false);
-    m.def("rowsum_f64", [](uintptr_t A, int64_t ld, int64_t nrows, uintptr_t out, uintptr_t stream, bool bf16) {
-        if (bf16)
+       py::arg("stream"), py::arg("bf16") = false, py::arg("f16") = false, py::arg("rinv") = 0);
+    m.def("rowsum_f64", [](uintptr_t A, int64_t ld, int64_t nrows, uintptr_t out, uintptr_t stream, bool bf16,
+                           bool f16, uintptr_t rinv) {
+        if (f16 && bf16) throw std::runtime_error("rowsum_f64: bf16 and f16 are exclusive");
+        if (f16)
+            sart::launch_rowsum_f64(P<const sart::f16s_t>(A), ld, nrows, P<double>(out), S(stream),
+                                    P<const float>(rinv));
+        else if (bf16)
             sart::launch_rowsum_f64(P<const sart::bf16_t>(A), ld, nrows, P<double>(out), S(stream));
         else
             sart::launch_rowsum_f64(P<const float>(A), ld, nrows, P<double>(out), S(stream));
-    }, py::arg("A"), py::arg("ld"), py::arg("nrows"), py::arg("out"), py::arg("stream"), py::arg("bf16") = false);
+    }, py::arg("A"), py::arg("ld"), py::arg("nrows"), py::arg("out"), py::arg("stream"), py::arg("bf16") = false,
+       py::arg("f16") = false, py::arg("rinv") = 0);
     m.def("backproject_num_splits", &sart::backproject_num_splits, py::arg("ld"), py::arg("nrows"),
           py::arg("elem_bytes") = 4);
     m.def("backproject", [](uintptr_t A, int64_t ld, int64_t nrows, uintptr_t w, int nsplit, uintptr_t partial,
-                            uintptr_t st, uintptr_t stream, bool bf16) {
-        if (bf16)
+                            uintptr_t st, uintptr_t stream, bool bf16, bool f16) {
+        if (f16 && bf16) throw std::runtime_error("backproject: bf16 and f16 are exclusive");
+        if (f16)  // w carries the rows' inverse scales
+            sart::launch_backproject(P<const sart::f16s_t>(A), ld, nrows, P<const float>(w), nsplit,
+                                     P<float>(partial), P<const sart::SartState>(st), S(stream));
+        else if (bf16)
             sart::launch_backproject(P<const sart::bf16_t>(A), ld, nrows, P<const float>(w), nsplit,
                                      P<float>(partial), P<const sart::SartState>(st), S(stream));
         else
             sart::launch_backproject(P<const float>(A), ld, nrows, P<const float>(w), nsplit, P<float>(partial),
                                      P<const sart::SartState>(st), S(stream));
     }, py::arg("A"), py::arg("ld"), py::arg("nrows"), py::arg("w"), py::arg("nsplit"), py::arg("partial"),
-       py::arg("st"), py::arg("stream"), py::arg("bf16") = false);
+       py::arg("st"), py::arg("stream"), py::arg("bf16") = false, py::arg("f16") = false);
     m.def("colsum_f64", [](uintptr_t A, int64_t ld, int64_t nrows, int nsplit, uintptr_t partial, uintptr_t stream,
-                           bool bf16) {
-        if (bf16)
+                           bool bf16, bool f16, uintptr_t rinv) {
+        if (f16 && bf16) throw std::runtime_error("colsum_f64: bf16 and f16 are exclusive");
+        if (f16)
+            sart::launch_colsum_f64(P<const sart::f16s_t>(A), ld, nrows, nsplit, P<double>(partial), S(stream),
+                                    P<const float>(rinv));
+        else if (bf16)
             sart::launch_colsum_f64(P<const sart::bf16_t>(A), ld, nrows, nsplit, P<double>(partial), S(stream));
         else
             sart::launch_colsum_f64(P<const float>(A), ld, nrows, nsplit, P<double>(partial), S(stream));
     }, py::arg("A"), py::arg("ld"), py::arg("nrows"), py::arg("nsplit"), py::arg("partial"), py::arg("stream"),
-       py::arg("bf16") = false);
+       py::arg("bf16") = false, py::arg("f16") = false, py::arg("rinv") = 0);
+    // fp32 block of whole rows [n][ld] -> row-scaled f16 bits, scales and inverse scales (n each); flushed: optional
+    // device counters (two uint64: the non-zero inputs stored as zero or subnormal, all non-zero inputs)
+    m.def("f32_to_f16_rows", [](uintptr_t src, int64_t n, int64_t ld, int64_t nvoxel, uintptr_t dst, uintptr_t scale,
+                                uintptr_t inv_scale, uintptr_t flushed, uintptr_t stream) {
+        sart::launch_f32_to_f16_rows(P<const float>(src), n, ld, nvoxel, P<sart::f16s_t>(dst), P<float>(scale),
+                                     P<float>(inv_scale), P<unsigned long long>(flushed), S(stream));
+    }, py::arg("src"), py::arg("n"), py::arg("ld"), py::arg("nvoxel"), py::arg("dst"), py::arg("scale"),
+       py::arg("inv_scale"), py::arg("flushed"), py::arg("stream"));
+    m.def("scale_rows", [](uintptr_t v, uintptr_t rinv, int64_t n, uintptr_t stream) {
+        sart::launch_scale_rows(P<float>(v), P<const float>(rinv), n, S(stream));
+    });
     m.def("f32_to_bf16", [](uintptr_t src, int64_t n, uintptr_t dst, uintptr_t stream) {
         sart::launch_f32_to_bf16(P<const float>(src), n, P<sart::bf16_t>(dst), S(stream));
     });
@@ -531,7 +567,7 @@ PYBIND11_MODULE(_sart_hip, m) {
         d["mw"] = k.mw;
         return d;
     };
-    // path: "fp32", "b16", "x3" or "h16"; nsplit 0: the planner's split count (what the engine allocates for)
+    // path: "fp32", "b16", "x3", "h16" or "s16"; nsplit 0: the planner's split count (what the engine allocates for)
     m.def("mf_plan_forward", [key_dict](const std::string& path, int nf, int64_t ld, int64_t nrows_pad, int nsplit) {
         const sart::MfFwdPlan p = sart::mf_plan_forward(sart::mf_path_from_name(path), nf, ld, nrows_pad,
                                                         sart::MfKnobs::from_env(), nsplit);
@@ -637,6 +673,27 @@ PYBIND11_MODULE(_sart_hip, m) {
     }, py::arg("A"), py::arg("ld"), py::arg("nrows"), py::arg("nrows_pad"), py::arg("X1"), py::arg("X2"),
        py::arg("Fout"), py::arg("nsplit"), py::arg("stream"), py::arg("nf"), py::arg("xblk"), py::arg("rsc"),
        py::arg("xinv"));
+    m.def("mf_forward_s16", [fwd_plan](uintptr_t A, int64_t ld, int64_t nrows, int64_t nrows_pad, uintptr_t X1,
+                                       uintptr_t X2, uintptr_t Fout, int nsplit, uintptr_t stream, int nf, bool xblk,
+                                       uintptr_t rsc, uintptr_t xinv) {
+        sart::launch_mf_forward_s16(fwd_plan(sart::MfPath::s16, nf, ld, nrows_pad, nsplit, "mf_forward_s16"),
+                                    P<const sart::f16s_t>(A), nrows, P<const uint16_t>(X1), P<const uint16_t>(X2),
+                                    P<float>(Fout), S(stream), xblk, P<const float>(rsc), P<const float>(xinv));
+    }, py::arg("A"), py::arg("ld"), py::arg("nrows"), py::arg("nrows_pad"), py::arg("X1"), py::arg("X2"),
+       py::arg("Fout"), py::arg("nsplit"), py::arg("stream"), py::arg("nf"), py::arg("xblk"), py::arg("rsc"),
+       py::arg("xinv"));
+    m.def("mf_backproject_s16", [bwd_plan](uintptr_t A, int64_t ld, int64_t nrows, uintptr_t W1, uintptr_t W2,
+                                           int64_t ldw, int nsplit, uintptr_t partial, uintptr_t stream, int nf,
+                                           int64_t v0, int64_t v1, uintptr_t inv_scale) {
+        sart::launch_mf_backproject_s16(bwd_plan(sart::MfPath::s16, nf, ld, nrows, nsplit, "mf_backproject_s16"),
+                                        P<const sart::f16s_t>(A), P<const uint16_t>(W1), P<const uint16_t>(W2), ldw,
+                                        P<float>(partial), S(stream), v0, v1, P<const float>(inv_scale));
+    }, py::arg("A"), py::arg("ld"), py::arg("nrows"), py::arg("W1"), py::arg("W2"), py::arg("ldw"), py::arg("nsplit"),
+       py::arg("partial"), py::arg("stream"), py::arg("nf"), py::arg("v0"), py::arg("v1"), py::arg("inv_scale"));
+    m.def("mf_scale_w_rows", [](uintptr_t W, uintptr_t rinv, int64_t nrows_pad, int nf, uintptr_t out,
+                                uintptr_t stream) {
+        sart::launch_mf_scale_w_rows(P<const float>(W), P<const float>(rinv), nrows_pad, nf, P<float>(out), S(stream));
+    });
     m.def("mf_split_w", [](uintptr_t W, int64_t nrows_pad, int nf, int64_t ldw, uintptr_t hi, uintptr_t lo,
                            uintptr_t stream, bool three) {
         sart::launch_mf_split_w(P<const float>(W), nrows_pad, nf, ldw, P<sart::bf16_t>(hi), P<sart::bf16_t>(lo),

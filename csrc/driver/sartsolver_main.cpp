@@ -71,10 +71,14 @@ bool file_exists(const std::string& p) {
 
 // Device-resident row shard [nrows_pad x ld] filled by streaming HDF5 row blocks through two pinned
 // buffers: block k+1 is read on a helper thread while block k is copied host -> HBM. bf16 (--rtm_bf16):
-// each block lands in an fp32 staging buffer in HBM and is rounded into the bf16 shard on the device.
+// each block lands in an fp32 staging buffer in HBM and is rounded into the bf16 shard on the device; f16
+// (--rtm_f16): likewise, by the row-scaling conversion kernel, which also writes the rows' scales (rsc) and counts
+// the non-zeros it stores as zero or subnormal.
 struct DeviceShard {
-    void* A = nullptr;  // fp32, or bf16 bit patterns when bf16
-    bool bf16 = false;
+    void* A = nullptr;  // fp32, or bf16 bit patterns when bf16, or row-scaled f16 bits when f16
+    bool bf16 = false, f16 = false;
+    DeviceArray<float> rsc;        // f16: [nrows_pad] row scales, then [nrows_pad] inverses
+    DeviceArray<uint64_t> counts;  // f16: [0] non-zeros stored as zero / subnormal, [1] non-zeros
     int64_t nrows = 0, nrows_pad = 0, nvoxel = 0, ld = 0;
     ~DeviceShard() {
         if (A) (void)hipFree(A);
@@ -93,6 +97,7 @@ struct LoadStats {
     double rss_hwm_before_mb = 0, rss_hwm_after_mb = 0, rss_after_setup_mb = 0, rss_after_first_read_mb = 0;
     // setup checkpoints (VmHWM, MiB): after the device allocation, after its zero fill, after the pinned staging
     double rss_after_malloc_mb = 0, rss_after_memset_mb = 0, rss_after_pinned_mb = 0;
+    uint64_t f16_flushed = 0, f16_nonzeros = 0;  // --rtm_f16: non-zeros stored as zero / subnormal, all non-zeros
 };
 
 double rss_hwm_mb() {  // VmHWM of this process, MiB (0 where /proc is unavailable)
@@ -110,7 +115,7 @@ double seconds_since(std::chrono::steady_clock::time_point t0) {
 // col0 / ncols: only that voxel block of every row (--partition_voxels), read as a column hyperslab.
 std::unique_ptr<DeviceShard> load_device_shard(const InputSet& in, uint64_t row0, uint64_t nrows, size_t block_bytes,
                                                uint64_t col0 = 0, uint64_t ncols = 0, bool bf16 = false,
-                                               LoadStats* stats = nullptr) {
+                                               bool f16 = false, LoadStats* stats = nullptr) {
     LoadStats ls;
     // The HIP runtime's one-time host footprint is not the loader's: its first kernel launch (code objects, device
     // queues: ~0.4 GB of resident memory on the MI355X box), its first pitched host -> device copy and the copy
@@ -134,12 +139,20 @@ std::unique_ptr<DeviceShard> load_device_shard(const InputSet& in, uint64_t row0
     const auto t_load = std::chrono::steady_clock::now();
     auto sh = std::make_unique<DeviceShard>();
     sh->bf16 = bf16;
+    sh->f16 = f16;
+    const bool stored16 = bf16 || f16;
     if (ncols == 0) ncols = in.nvoxel - col0;
     sh->nrows = (int64_t)nrows;
     sh->nvoxel = (int64_t)ncols;
-    sh->ld = choose_ld(sh->nvoxel, 0.10, !bf16);  // bf16 shards keep the 8-KiB slabs of their tiles
+    sh->ld = choose_ld(sh->nvoxel, 0.10, !stored16);  // 16-bit shards keep the 8-KiB slabs of their tiles
     sh->nrows_pad = (sh->nrows + 63) / 64 * 64;
-    const size_t bytes = (size_t)sh->nrows_pad * sh->ld * (bf16 ? sizeof(bf16_t) : sizeof(float));
+    const size_t bytes = (size_t)sh->nrows_pad * sh->ld * (stored16 ? sizeof(bf16_t) : sizeof(float));
+    if (f16) {  // scale 1 for the padding rows (the conversion writes the rows it sees)
+        sh->rsc.resize(2 * (size_t)sh->nrows_pad);
+        sh->counts.resize(2);
+        const std::vector<float> ones(2 * (size_t)sh->nrows_pad, 1.f);
+        hip_ok(hipMemcpy(sh->rsc.get(), ones.data(), ones.size() * sizeof(float), hipMemcpyHostToDevice), "H2D scales");
+    }
     hip_ok(hipMalloc(&sh->A, bytes), "hipMalloc(RTM shard)");
     ls.rss_after_malloc_mb = rss_hwm_mb();
     // on the copy stream: a fill on the null stream would bring up that stream's device queue (~0.19 GB resident)
@@ -158,9 +171,9 @@ std::unique_ptr<DeviceShard> load_device_shard(const InputSet& in, uint64_t row0
     float* buf[2] = {nullptr, nullptr};
     for (auto& b : buf) hip_ok(hipHostMalloc(reinterpret_cast<void**>(&b), rows_per_block * V * sizeof(float)), "hipHostMalloc");
     ls.rss_after_pinned_mb = rss_hwm_mb();
-    // bf16: fp32 staging rows [rows_per_block x ld], padding columns zero (the 2-D copies write ncols only)
+    // bf16 / f16: fp32 staging rows [rows_per_block x ld], padding columns zero (the 2-D copies write ncols only)
     DeviceArray<float> stage;
-    if (bf16) stage.resize(rows_per_block * (size_t)sh->ld);
+    if (stored16) stage.resize(rows_per_block * (size_t)sh->ld);
     hipEvent_t ev[2];
     for (auto& e : ev) hip_ok(hipEventCreateWithFlags(&e, hipEventDisableTiming), "hipEventCreate");
     bool ev_used[2] = {false, false};
@@ -202,13 +215,18 @@ std::unique_ptr<DeviceShard> load_device_shard(const InputSet& in, uint64_t row0
                 next = std::async(std::launch::async, read_into, k + 1, buf[nb]);
             }
             const uint64_t r0 = blocks[k].first, nr = blocks[k].second - blocks[k].first;
-            float* dst = bf16 ? stage.get() : static_cast<float*>(sh->A) + r0 * sh->ld;
+            float* dst = stored16 ? stage.get() : static_cast<float*>(sh->A) + r0 * sh->ld;
             hip_ok(hipEventRecord(tev[2 * k], s), "event");
             hip_ok(hipMemcpy2DAsync(dst, sh->ld * sizeof(float), cur, V * sizeof(float), ncols * sizeof(float), nr,
                                     hipMemcpyHostToDevice, s),
                    "H2D RTM block");
             hip_ok(hipEventRecord(tev[2 * k + 1], s), "event");
-            if (bf16)  // stream-ordered: the next block's copy into the staging rows waits for this conversion
+            if (f16)  // (stream-ordered like the bf16 rounding below)
+                launch_f32_to_f16_rows(stage.get(), (int64_t)nr, sh->ld, sh->nvoxel,
+                                       static_cast<f16s_t*>(sh->A) + r0 * sh->ld, sh->rsc.get() + r0,
+                                       sh->rsc.get() + sh->nrows_pad + r0,
+                                       reinterpret_cast<unsigned long long*>(sh->counts.get()), s);
+            else if (bf16)  // stream-ordered: the next block's copy into the staging rows waits for this conversion
                 launch_f32_to_bf16(stage.get(), (int64_t)nr * sh->ld, static_cast<bf16_t*>(sh->A) + r0 * sh->ld, s);
             hip_ok(hipEventRecord(ev[k % 2], s), "event");
             ev_used[k % 2] = true;
@@ -219,6 +237,12 @@ std::unique_ptr<DeviceShard> load_device_shard(const InputSet& in, uint64_t row0
             }
         }
         hip_ok(hipStreamSynchronize(s), "RTM upload");
+        if (f16) {
+            uint64_t c[2] = {0, 0};
+            hip_ok(hipMemcpy(c, sh->counts.get(), sizeof(c), hipMemcpyDeviceToHost), "D2H f16 counts");
+            ls.f16_flushed = c[0];
+            ls.f16_nonzeros = c[1];
+        }
     } catch (...) {
         (void)hipStreamSynchronize(s);
         release();
@@ -430,7 +454,7 @@ int main(int argc, char** argv) {
         // --rtm_format: the single-frame GPU solver on pixel-row shards of fp32 values can keep a sparse RTM sparse
         // (decided from the files' metadata: the same on every rank)
         bool sparse = false;
-        if (!cols && !cfg.rtm_bf16 && cfg.rtm_format != "dense") {
+        if (!cols && !cfg.rtm_bf16 && !cfg.rtm_f16 && cfg.rtm_format != "dense") {
             const double dens = rtm_sparse_density(in.rtm_files, in.rtm_name, in.npixel, in.nvoxel);
             // auto: the sparse kernels read 16 bytes per non-zero and sweep (CSR + CSC, index + value) against 4 bytes
             // per element for the dense fused sweep; measured at 32768 x 32768 (uniform random positions): sparse /
@@ -458,7 +482,7 @@ int main(int argc, char** argv) {
                 sshard = load_sparse_shard(in, blk.offset, blk.size, &lstats);
             else if (gpu)
                 dshard = load_device_shard(in, blk.offset, blk.size, block_bytes, vblk.offset, vblk.size,
-                                           cfg.rtm_bf16, &lstats);
+                                           cfg.rtm_bf16, cfg.rtm_f16, &lstats);
             else {
                 hshard.assign(blk.size * in.nvoxel, 0.f);
                 RtmReader(in.rtm_files, in.rtm_name, in.nvoxel)
@@ -485,7 +509,7 @@ int main(int argc, char** argv) {
             EngineConfig ec;
             static_cast<SolverParams&>(ec) = params;
             ec.conv_tolerance *= tol_factor;
-            ec.use_fused = !cfg.two_pass;
+            ec.use_fused = !cfg.two_pass && !cfg.rtm_f16;  // f16 shards: the two-pass kernels (no fused f16 sweep yet)
             ec.fused_min_bytes = fused_min_bytes_from_env();
             if (const char* v = std::getenv("SART_FUSED_VARIANT"); v && *v) ec.fused_variant = std::atoi(v);
             ec.time_collectives = !cfg.profile_file.empty();  // --profile: GPU time in the all-reduces per frame
@@ -500,6 +524,8 @@ int main(int argc, char** argv) {
                                              sshard->nvoxel, (sshard->nvoxel + 63) / 64 * 64, dcomm.get(), ec, &view);
             } else {
                 ec.rtm_bf16 = dshard->bf16;
+                ec.rtm_f16 = dshard->f16;
+                ec.row_scale = dshard->rsc.get();
                 e = std::make_unique<Engine>(device, dshard->A, dshard->nrows, dshard->nrows_pad, dshard->nvoxel,
                                              dshard->ld, dcomm.get(), ec);
             }
@@ -524,6 +550,8 @@ int main(int argc, char** argv) {
                                                         ec, &view);
             } else {
                 ec.rtm_bf16 = dshard->bf16;  // bf16 MFMA projections
+                ec.rtm_f16 = dshard->f16;    // the same kernels on the f16 MFMA
+                ec.row_scale = dshard->rsc.get();
                 mf = std::make_unique<MultiFrameEngine>(device, dshard->A, dshard->nrows, dshard->nrows_pad,
                                                         dshard->nvoxel, dshard->ld, dcomm.get(), ec);
             }
@@ -582,6 +610,15 @@ int main(int argc, char** argv) {
             double sm[5] = {(double)lstats.bytes, lstats.read_s, lstats.h2d_s, lstats.wait_read_s, lstats.wait_copy_s};
             host->all_reduce_host(mx, 4, ReduceOp::kMax);
             host->all_reduce_host(sm, 5, ReduceOp::kSum);
+            // f16 storage: the non-zeros stored as zero / subnormal and all non-zeros, summed over the ranks
+            double fl[2] = {(double)lstats.f16_flushed, (double)lstats.f16_nonzeros};
+            host->all_reduce_host(fl, 2, ReduceOp::kSum);
+            const std::string storage = !gpu || sparse ? "fp32" : (cfg.rtm_f16 ? "f16" : (cfg.rtm_bf16 ? "bf16" : "fp32"));
+            std::string path = "cpu";
+            if (mf)
+                path = "multi-frame " + mf->forward_split() + " / " + mf->backproject_split();
+            else if (engine)
+                path = sparse ? "sparse two-pass" : (engine->use_fused() ? "fused" : "two-pass");
             if (profile.is_open())
                 profile << "{\"load\": true, \"load_s\": " << mx[0] << ", \"rtm_GB\": " << sm[0] / 1e9
                         << ", \"load_GBps\": " << (mx[0] > 0 ? sm[0] / 1e9 / mx[0] : 0.0)
@@ -605,6 +642,9 @@ int main(int argc, char** argv) {
                         << ", \"rss_growth_MB_max\": " << mx[1] << ", \"shard_MB_max\": " << mx[3] / 1048576.0
                         << ", \"sparse\": " << (in.has_sparse ? "true" : "false")
                         << ", \"rtm_format\": \"" << (sparse ? "sparse" : "dense") << "\""
+                        << ", \"rtm_storage\": \"" << storage << "\", \"f16_flushed\": " << (uint64_t)fl[0]
+                        << ", \"f16_flushed_fraction\": " << (fl[1] > 0 ? fl[0] / fl[1] : 0.0)
+                        << ", \"solver_path\": \"" << json_escape(path) << "\""
                         << ", \"nnz\": " << (sparse ? (gpu ? sshard->nnz : cpu_nnz) : 0) << ", \"driver\": \"native\"}\n";
         }
 
@@ -848,7 +888,7 @@ int main(int argc, char** argv) {
                     const double secs = info.ms > 0 ? 1e-3 * info.ms : 1e-3 * ms;
                     const double pv = (double)in.npixel * (double)in.nvoxel;
                     const double reads = gpu && info.used_fused ? 1.0 : 2.0;
-                    const double elem = gpu && cfg.rtm_bf16 ? 2.0 : 4.0;  // bytes per stored RTM element
+                    const double elem = gpu && (cfg.rtm_bf16 || cfg.rtm_f16) ? 2.0 : 4.0;  // bytes per stored RTM element
                     profile << "{\"frame\": " << cur << ", \"time\": " << image.frame_time(cur)
                             << ", \"status\": " << info.status << ", \"iterations\": " << info.iterations
                             << ", \"convergence\": " << info.convergence << ", \"sweeps\": " << sweeps

@@ -81,8 +81,10 @@ Engine::Engine(int device, const void* A, int64_t nrows, int64_t nrows_pad, int6
     : device_(device), A_(A), P_(nrows), Pp_(nrows_pad), V_(nvoxel), ld_(ld), comm_(comm), cfg_(cfg) {
     validate_params(cfg_);
     if (!comm_) throw std::invalid_argument("Engine: communicator required");
+    if (cfg_.rtm_f16 && cfg_.rtm_bf16)
+        throw std::invalid_argument("Engine: rtm_f16 and rtm_bf16 are exclusive (one storage format per shard)");
     if (sparse) {
-        if (cfg_.column_shard || cfg_.rtm_bf16)
+        if (cfg_.column_shard || cfg_.rtm_bf16 || cfg_.rtm_f16)
             throw std::invalid_argument("Engine: a sparse shard is a row shard of fp32 values");
         if (!sparse->row_ptr || !sparse->col_ptr)
             throw std::invalid_argument("Engine: sparse shard needs its CSR and CSC arrays");
@@ -96,6 +98,15 @@ Engine::Engine(int device, const void* A, int64_t nrows, int64_t nrows_pad, int6
     }
     if (ld_ % 64 || ld_ < V_ || Pp_ % 64 || Pp_ < P_)
         throw std::invalid_argument("Engine: ld and nrows_pad must be multiples of 64 covering the shard");
+    if (cfg_.rtm_f16) {
+        if (cfg_.column_shard) throw std::invalid_argument("Engine: row-scaled f16 storage is for row shards");
+        if (!cfg_.row_scale)
+            throw std::invalid_argument("Engine: an f16 shard needs its row scales (EngineConfig::row_scale)");
+        if (cfg_.use_fused)
+            throw std::invalid_argument("Engine: the fused f16 sweep is not built yet; f16 shards run the two-pass "
+                                        "kernels (use_fused = false)");
+        rinv_ = cfg_.row_scale + Pp_;
+    }
     cfg_.check_interval = std::max(1, cfg_.check_interval);
     if (cfg_.column_shard) {
         if (cfg_.nvoxel_total <= 0) cfg_.nvoxel_total = V_;
@@ -121,7 +132,7 @@ Engine::Engine(int device, const void* A, int64_t nrows, int64_t nrows_pad, int6
     if (const char* t = std::getenv("SART_TAIL_FUSED"); t && *t) tail_fused_ = std::atoi(t) != 0;
 
     // the sparse back-projection writes complete column sums: one partial row
-    nsplit_ = sparse_ ? 1 : backproject_num_splits(ld_, Pp_, cfg_.rtm_bf16 ? 2 : 4);
+    nsplit_ = sparse_ ? 1 : backproject_num_splits(ld_, Pp_, (cfg_.rtm_bf16 || cfg_.rtm_f16) ? 2 : 4);
     comm_buf_.resize(ld_ + 64);  // [0, ld) correction, [ld] ||A x||^2
     x_.resize(ld_);
     pen_.resize(ld_);
@@ -227,7 +238,8 @@ void Engine::alloc_fused() {
 }
 
 void DeviceRaySums::compute(const void* A, int64_t P, int64_t Pp, int64_t V, int64_t ld, Communicator* comm,
-                            const SolverParams& p, hipStream_t stream, bool col_shard, bool a_bf16) {
+                            const SolverParams& p, hipStream_t stream, bool col_shard, bool a_bf16,
+                            const float* f16_rinv) {
     // rho_v = sum_p A[p, v] (fp64, all-reduced), l_p = sum_v A[p, v] (fp64, local): on the device instead of
     // the reference's host loops (sartsolver.cpp:38-56); scales with the reference's fp32 semantics
     RoctxRange r("sart::ray_sums");
@@ -235,10 +247,13 @@ void DeviceRaySums::compute(const void* A, int64_t P, int64_t Pp, int64_t V, int
     rho64.resize(ld);
     ray_len.resize(Pp);
     for (auto* b : {&dinv, &dscale, &dmask}) b->resize(ld);
-    const int nsplit = backproject_num_splits(ld, Pp, a_bf16 ? 2 : 4);
+    const int nsplit = backproject_num_splits(ld, Pp, (a_bf16 || f16_rinv) ? 2 : 4);
     {
         DeviceArray<double> part((size_t)nsplit * ld);
-        if (a_bf16) {
+        if (f16_rinv) {  // row-scaled f16: sums of H / s_p
+            launch_rowsum_f64(static_cast<const f16s_t*>(A), ld, P, ell64.get(), stream, f16_rinv);
+            launch_colsum_f64(static_cast<const f16s_t*>(A), ld, P, nsplit, part.get(), stream, f16_rinv);
+        } else if (a_bf16) {
             launch_rowsum_f64(static_cast<const bf16_t*>(A), ld, P, ell64.get(), stream);
             launch_colsum_f64(static_cast<const bf16_t*>(A), ld, P, nsplit, part.get(), stream);
         } else {
@@ -290,7 +305,7 @@ void Engine::ray_sums() {
     if (sparse_)
         rs_.compute_sparse(sp_, P_, Pp_, V_, ld_, comm_, cfg_, stream_);
     else
-        rs_.compute(A_, P_, Pp_, V_, ld_, comm_, cfg_, stream_, cfg_.column_shard, cfg_.rtm_bf16);
+        rs_.compute(A_, P_, Pp_, V_, ld_, comm_, cfg_, stream_, cfg_.column_shard, cfg_.rtm_bf16, rinv_);
 }
 
 void Engine::fwd(int epi, const float* x, float* out_f, float* out_w, double* Fpart, const SartState* st) {
@@ -298,6 +313,9 @@ void Engine::fwd(int epi, const float* x, float* out_f, float* out_w, double* Fp
     const float* arow = epi == kEpiPlain ? nullptr : arow_.get();
     if (sparse_)
         launch_csr_forward(epi, sp_, P_, Pp_, x, ghat, arow, out_f, out_w, Fpart, st, stream_);
+    else if (cfg_.rtm_f16)
+        launch_forward(epi, static_cast<const f16s_t*>(A_), ld_, P_, Pp_, x, ghat, arow, out_f, out_w, Fpart, st,
+                       stream_, rinv_);
     else if (cfg_.rtm_bf16)
         launch_forward(epi, static_cast<const bf16_t*>(A_), ld_, P_, Pp_, x, ghat, arow, out_f, out_w, Fpart, st,
                        stream_);
@@ -309,6 +327,8 @@ void Engine::fwd(int epi, const float* x, float* out_f, float* out_w, double* Fp
 void Engine::bwd(const float* w, const SartState* st) {
     if (sparse_)
         launch_csc_backproject(sp_, V_, w, partial_.get(), st, stream_);  // nsplit_ == 1
+    else if (cfg_.rtm_f16)  // w carries the rows' 1 / s_p
+        launch_backproject(static_cast<const f16s_t*>(A_), ld_, P_, w, nsplit_, partial_.get(), st, stream_);
     else if (cfg_.rtm_bf16)
         launch_backproject(static_cast<const bf16_t*>(A_), ld_, P_, w, nsplit_, partial_.get(), st, stream_);
     else
@@ -397,6 +417,10 @@ double Engine::setup_frame(const double* g, const double* x0, bool x0_on_device)
     if (P_) hip_ok(hipMemcpyAsync(g64_.get(), hg_, P_ * sizeof(double), hipMemcpyHostToDevice, stream_), "H2D g");
     launch_prep_rows(g64_.get(), P_, Pp_, 1.0 / norm, rs_.ray_len.get(), (float)cfg_.ray_length_threshold, ghat_.get(),
                      arow_.get(), gpos_.get(), wo_.get(), stream_);
+    if (cfg_.rtm_f16) {  // the back-projections below meet A s_p: their row operands take 1 / s_p
+        if (!x0) launch_scale_rows(gpos_.get(), rinv_, Pp_, stream_);
+        if (cfg_.logarithmic) launch_scale_rows(wo_.get(), rinv_, Pp_, stream_);
+    }
     if (!x0) {
         // cold start x0 = [rho > tau] A^T max(ghat, 0) / rho (reference sart_kernels.cu:22-60)
         bwd(gpos_.get(), nullptr);

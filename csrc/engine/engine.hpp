@@ -66,6 +66,14 @@ struct EngineConfig : SolverParams {
     // Fused sweep variant 6 (bf16 register tiles, fp32 LDS ring), the two-pass kernels, or the bf16 MFMA
     // multi-frame kernels.
     bool rtm_bf16 = false;
+    // Row-scaled f16 storage (exclusive with rtm_bf16): A holds f16 bit patterns of A[p][v] s_p with a power-of-two
+    // scale per row (sart_common.hpp f16s_t; 11 significant bits at bf16's two bytes), row_scale the device array
+    // written with the shard by launch_f32_to_f16_rows: [nrows_pad] scales, then [nrows_pad] inverses (not owned).
+    // The solve is exact SART for the matrix H / s_p: ray sums are taken over it, every product and sum stays fp32 /
+    // fp64. Two-pass kernels (use_fused must be false: no fused f16 sweep yet) and the f16-storage MFMA multi-frame
+    // kernels; row shards only.
+    bool rtm_f16 = false;
+    const float* row_scale = nullptr;
     // Multi-frame engine with an fp32 shard: run the projections on the bf16 matrix cores with A split into
     // hi + lo bf16 in registers (three products per element; multiframe_bf16.hip, "split-A") instead of fp32
     // MFMA. 1: on, 0: off, -1: env SART_MF_X3 (0 / 1), else on for batches of 32 and 64 frames (where fp32
@@ -104,9 +112,10 @@ class DeviceArray {
 // accumulation, global column sums all-reduced): shared by the single- and multi-frame engines.
 struct DeviceRaySums {
     // col_shard: the shard holds all rows of some columns, so the row sums are all-reduced instead
-    // A: fp32 shard, or bf16 bit patterns when a_bf16
+    // A: fp32 shard, or bf16 bit patterns when a_bf16, or row-scaled f16 bits with f16_rinv their inverse row scales
     void compute(const void* A, int64_t P, int64_t Pp, int64_t V, int64_t ld, Communicator* comm,
-                 const SolverParams& p, hipStream_t stream, bool col_shard = false, bool a_bf16 = false);
+                 const SolverParams& p, hipStream_t stream, bool col_shard = false, bool a_bf16 = false,
+                 const float* f16_rinv = nullptr);
     // the same from a sparse shard (CSR row sums, CSC column sums)
     void compute_sparse(const SparseRtm& s, int64_t P, int64_t Pp, int64_t V, int64_t ld, Communicator* comm,
                         const SolverParams& p, hipStream_t stream);
@@ -130,8 +139,8 @@ double fused_min_bytes_from_env();
 
 class Engine {
    public:
-    // A: device pointer to the row-major shard [nrows_pad x ld] (fp32, or bf16 with cfg.rtm_bf16), zero
-    // padded (not owned).
+    // A: device pointer to the row-major shard [nrows_pad x ld] (fp32, bf16 with cfg.rtm_bf16, or row-scaled f16
+    // with cfg.rtm_f16 and cfg.row_scale), zero padded (not owned).
     // sparse: the shard as device CSR + CSC arrays instead (A null; csrc/kernels/sparse.hip, not owned): the two-pass
     // sweep on sparse kernels, row shards of fp32 values only
     Engine(int device, const void* A, int64_t nrows, int64_t nrows_pad, int64_t nvoxel, int64_t ld,
@@ -185,6 +194,7 @@ class Engine {
 
     int device_;
     const void* A_;
+    const float* rinv_ = nullptr;  // f16 shard: the rows' inverse scales (cfg_.row_scale + nrows_pad)
     bool sparse_ = false;
     SparseRtm sp_{};
     int64_t P_, Pp_, V_, ld_;

@@ -96,14 +96,15 @@ const char* mf_path_name(MfPath p) {
         case MfPath::fp32: return "fp32";
         case MfPath::b16: return "b16";
         case MfPath::x3: return "x3";
+        case MfPath::s16: return "s16";
         default: return "h16";
     }
 }
 
 MfPath mf_path_from_name(const std::string& name) {
-    for (MfPath p : {MfPath::fp32, MfPath::b16, MfPath::x3, MfPath::h16})
+    for (MfPath p : {MfPath::fp32, MfPath::b16, MfPath::x3, MfPath::h16, MfPath::s16})
         if (name == mf_path_name(p)) return p;
-    throw std::runtime_error("multi-frame path must be fp32, b16, x3 or h16, not '" + name + "'");
+    throw std::runtime_error("multi-frame path must be fp32, b16, x3, h16 or s16, not '" + name + "'");
 }
 
 // ------------------------------------------------------------------ the table of supported keys
@@ -117,6 +118,12 @@ const MfKey kVariants[] = {
 #undef X
 #define X(...) mf_key_fwd_a32(__VA_ARGS__),
     MF_FWD_A32_VARIANTS(X)
+#undef X
+#define X(...) mf_key_fwd_s16(__VA_ARGS__),
+    MF_FWD_S16_VARIANTS(X)
+#undef X
+#define X(...) mf_key_bwd_s16(__VA_ARGS__),
+    MF_BWD_S16_VARIANTS(X)
 #undef X
 #define X(...) mf_key_bwd_f32(__VA_ARGS__),
     MF_BWD_F32_VARIANTS(X)
@@ -248,8 +255,17 @@ int bwd_b16_splits(const MfKnobs& k, int64_t ld, int64_t nrows, bool a32) {
     return clamp_splits(target, nblk, (nrows + 63) / 64);
 }
 
+// Row-scaled f16 storage runs the bf16-storage kernels (same bytes, same tiles): its key is the bf16-storage key of
+// the same shape and knobs under its own path. Its variant lists hold the default keys only, so a knob that moves
+// the bf16-storage key elsewhere throws in require_variant.
+MfKey as_s16(MfKey k) {
+    k.path = MfPath::s16;
+    return k;
+}
+
 MfKey fwd_key(MfPath path, int nf, int64_t ld, int64_t nrows_pad, const MfKnobs& k) {
     const int ng = nf / 16;
+    if (path == MfPath::s16) return as_s16(fwd_key(MfPath::b16, nf, ld, nrows_pad, k));
     if (path == MfPath::fp32) {
         const int rt = (nrows_pad % 64 == 0) ? f32_rows(k) : 2;  // a wave's 16 * rt rows lie inside the padding
         return mf_key_fwd_f32(ng, f32_depth(k, true, nf), rt, k.nt);
@@ -282,6 +298,7 @@ MfKey fwd_key(MfPath path, int nf, int64_t ld, int64_t nrows_pad, const MfKnobs&
 
 MfKey bwd_key(MfPath path, int nf, int64_t ld, const MfKnobs& k) {
     const int ng = nf / 16;
+    if (path == MfPath::s16) return as_s16(bwd_key(MfPath::b16, nf, ld, k));
     if (path == MfPath::fp32) return mf_key_bwd_f32(ng, f32_depth(k, false, nf), f32_vox(k, ld, nf));
     if (path == MfPath::h16) {
         // SART_MF_H16 (A/B runs): "ew" early W loads, "w1" one wave per SIMD (512 registers), "ew,w1".
@@ -324,7 +341,7 @@ MfFwdPlan mf_plan_forward(MfPath path, int nf, int64_t ld, int64_t nrows_pad, co
     if (ld % 64 != 0) throw std::runtime_error(what + ": ld must be a multiple of 64");
     if (nsplit < 0) throw std::runtime_error(what + ": nsplit must be >= 1");
     check_nf(nf, what, path != MfPath::fp32);
-    const int pad = path == MfPath::h16 ? 64 : 32;
+    const int pad = (path == MfPath::h16 || path == MfPath::s16) ? 64 : 32;
     if (nrows_pad % pad != 0)
         throw std::runtime_error(what + ": padded rows must be a multiple of " + std::to_string(pad));
     MfFwdPlan p;
@@ -334,7 +351,8 @@ MfFwdPlan mf_plan_forward(MfPath path, int nf, int64_t ld, int64_t nrows_pad, co
     p.ld = ld;
     p.nrows_pad = nrows_pad;
     // bf16 storage: ~512 workgroups (see the back-projection)
-    p.nsplit = nsplit > 0 ? nsplit : fwd_splits(k, ld, nrows_pad, path == MfPath::b16 ? 512 : 0);
+    const bool stored16 = path == MfPath::b16 || path == MfPath::s16;  // two bytes per element in HBM
+    p.nsplit = nsplit > 0 ? nsplit : fwd_splits(k, ld, nrows_pad, stored16 ? 512 : 0);
     const int64_t unit = path == MfPath::fp32 ? 16 : 64;
     p.cps = ((ld + p.nsplit - 1) / p.nsplit + unit - 1) / unit * unit;
     const int64_t rows_per_block = 64 * p.key.tile;  // 4 waves x 16 RT rows per workgroup
@@ -347,7 +365,8 @@ MfBwdPlan mf_plan_backproject(MfPath path, int nf, int64_t ld, int64_t nrows, co
     if (ld % 64 != 0) throw std::runtime_error(what + ": ld must be a multiple of 64");
     if (nsplit < 0) throw std::runtime_error(what + ": nsplit must be >= 1");
     // 128 frames: bf16 storage and the f16 pairs (the bf16-piece split-A engine takes the h16 back-projection)
-    check_nf(nf, what, path == MfPath::b16 || path == MfPath::h16);
+    const bool stored16 = path == MfPath::b16 || path == MfPath::s16;  // two bytes per element in HBM
+    check_nf(nf, what, stored16 || path == MfPath::h16);
     MfBwdPlan p;
     p.key = bwd_key(path, nf, ld, k);
     require_variant(p.key, k);
@@ -359,10 +378,10 @@ MfBwdPlan mf_plan_backproject(MfPath path, int nf, int64_t ld, int64_t nrows, co
         p.rps = ((nrows + p.nsplit - 1) / p.nsplit + 15) / 16 * 16;
         p.vox_align = 64 * p.key.tile;
     } else {
-        p.nsplit = nsplit > 0 ? nsplit : bwd_b16_splits(k, ld, nrows, path != MfPath::b16);
+        p.nsplit = nsplit > 0 ? nsplit : bwd_b16_splits(k, ld, nrows, !stored16);
         const int64_t nrows32 = (nrows + 31) / 32 * 32;
         p.rps = ((nrows32 + p.nsplit - 1) / p.nsplit + 31) / 32 * 32;
-        p.vox_align = 64 * split_vt(k, ld, path != MfPath::b16);
+        p.vox_align = 64 * split_vt(k, ld, !stored16);
     }
     return p;
 }
@@ -382,10 +401,10 @@ std::vector<std::pair<std::string, std::string>> mf_key_env(const MfKey& key) {
     if (key.path == MfPath::fp32) {
         e = {{"SART_MF_DEPTH", d}, {key.forward ? "SART_MF_ROWS" : "SART_MF_VOX", t}};
         if (key.forward) e.push_back({"SART_MF_NT", key.nt ? "1" : "0"});
-    } else if (key.path == MfPath::b16 && key.forward) {
+    } else if ((key.path == MfPath::b16 || key.path == MfPath::s16) && key.forward) {
         e = {{"SART_MF_DEPTH", d}, {"SART_MF_B16_FWD", tile_str({key.tile, key.kb, key.lds, key.as}, true)},
              {"SART_MF_XEARLY", key.early ? "1" : "0"}};
-    } else if (key.path == MfPath::b16) {
+    } else if (key.path == MfPath::b16 || key.path == MfPath::s16) {
         e = {{"SART_MF_DEPTH", d}, {"SART_MF_B16_VT", t + (key.lds ? ",lds" : ",reg")},
              {"SART_MF_WEARLY", key.early ? "1" : "0"}};
     } else if (key.forward) {

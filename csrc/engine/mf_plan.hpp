@@ -26,7 +26,8 @@
 namespace sart {
 
 // fp32: fp32 MFMA. b16: bf16 storage. x3: split-A on bf16 pieces (fp32 A split in registers). h16: split-A on f16 pairs.
-enum class MfPath { fp32, b16, x3, h16 };
+// s16: row-scaled f16 storage (the bf16-storage kernels on the f16 MFMA; the bf16-storage defaults, no knobs of its own).
+enum class MfPath { fp32, b16, x3, h16, s16 };
 
 // Forward tile "RT,KB[,lds][,as]": 16-row tiles per wave, 32-voxel blocks per step, X shared through LDS, A staged
 // through LDS in full row segments. rt == 0: not set (or malformed: ignored).
@@ -95,6 +96,12 @@ constexpr MfKey mf_key_fwd_b16(bool lds, int ng, int depth, int rt, int kb, bool
 constexpr MfKey mf_key_fwd_a32(bool h16, int ng, int depth, int rt, int kb, bool as, bool ex) {
     return {h16 ? MfPath::h16 : MfPath::x3, true, ng, depth, rt, kb, true, as, ex, false, 0};
 }
+constexpr MfKey mf_key_fwd_s16(int ng, int depth, int rt, int kb, bool as, bool ex) {
+    return {MfPath::s16, true, ng, depth, rt, kb, true, as, ex, false, 0};
+}
+constexpr MfKey mf_key_bwd_s16(int ng, int depth, int vt, bool ew) {
+    return {MfPath::s16, false, ng, depth, vt, 0, true, false, ew, false, 0};
+}
 constexpr MfKey mf_key_bwd_f32(int ng, int depth, int vt) {
     return {MfPath::fp32, false, ng, depth, vt, 0, false, false, false, false, 0};
 }
@@ -154,7 +161,7 @@ std::vector<MfKey> mf_variants(MfPath path, bool forward, int nf);
 // The knob setting that selects `key` (variable name, value), for the probes.
 std::vector<std::pair<std::string, std::string>> mf_key_env(const MfKey& key);
 
-MfPath mf_path_from_name(const std::string& name);  // "fp32", "b16", "x3", "h16"
+MfPath mf_path_from_name(const std::string& name);  // "fp32", "b16", "x3", "h16", "s16"
 const char* mf_path_name(MfPath p);
 
 // Split counts for given knobs (Python bindings mf_*_num_splits; the plans hold the same numbers).

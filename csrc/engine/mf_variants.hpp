@@ -48,6 +48,10 @@
     X(1, 4, 2, 2, 1, 1, 1) X(1, 4, 2, 2, 2, 0, 1) X(1, 4, 2, 2, 2, 1, 1) X(1, 4, 3, 2, 1, 1, 1) X(1, 4, 3, 2, 2, 1, 1) \
     X(1, 8, 2, 2, 1, 1, 1) X(1, 8, 2, 2, 2, 1, 1) X(1, 8, 3, 2, 1, 1, 1)
 
+// forward, row-scaled f16 storage: X(NG, DEPTH, RT, KB, AS, EX): k_mf_forward_b16_lds<NG, DEPTH, RT, KB, f16s_t, AS, EX>.
+// Only the keys the planner returns with no knob set (the bf16-storage defaults at 16 / 32 / 64 / 128 frames): (a).
+#define MF_FWD_S16_VARIANTS(X) X(1, 3, 2, 2, 0, 0) X(2, 3, 2, 2, 1, 0) X(4, 3, 4, 2, 0, 0) X(8, 3, 2, 2, 1, 0)
+
 // back-projection, fp32 MFMA: k_mf_backproject<NG, DEPTH, VT>
 #define MF_BWD_F32_VARIANTS(X) \
     X(1, 1, 1) X(1, 1, 2) X(1, 2, 1) X(1, 2, 2) X(1, 3, 1) X(1, 3, 2) \
@@ -69,6 +73,11 @@
     X(1, 2, 1, 0) X(1, 2, 1, 1) X(1, 2, 2, 0) X(1, 3, 1, 0) X(1, 3, 2, 0) X(2, 2, 1, 0) \
     X(2, 2, 1, 1) X(2, 2, 2, 0) X(2, 3, 1, 0) X(2, 3, 2, 0) X(4, 2, 1, 0) X(4, 2, 1, 1) \
     X(4, 2, 2, 0) X(4, 3, 1, 0) X(4, 3, 2, 0)
+
+// back-projection, row-scaled f16 storage: X(NG, DEPTH, VT, EW): k_mf_backproject_b16_lds<NG, DEPTH, VT, f16s_t, EW>.
+// The planner's defaults only: VT 2 (ld % 128 == 0) or 1 at 16 / 32 / 64 frames, VT 1 at 128; W loaded early.
+#define MF_BWD_S16_VARIANTS(X) \
+    X(1, 3, 1, 1) X(1, 3, 2, 1) X(2, 3, 1, 1) X(2, 3, 2, 1) X(4, 3, 1, 1) X(4, 3, 2, 1) X(8, 3, 1, 1)
 
 // back-projection, split-A on f16 pairs: k_mf_backproject_h16<NG, DEPTH, EW, MW>
 #define MF_BWD_H16_VARIANTS(X) \

@@ -33,11 +33,15 @@ int MultiFrameEngine::batch_width(int frames) {
 
 MultiFrameEngine::MultiFrameEngine(int device, const void* A, int64_t nrows, int64_t nrows_pad, int64_t nvoxel,
                                    int64_t ld, Communicator* comm, const EngineConfig& cfg, const SparseRtm* sparse)
-    : device_(device), A_(A), bf16_(cfg.rtm_bf16), P_(nrows), Pp_(nrows_pad), V_(nvoxel), ld_(ld), comm_(comm),
+    : device_(device), A_(A), bf16_(cfg.rtm_bf16), f16_(cfg.rtm_f16), P_(nrows), Pp_(nrows_pad), V_(nvoxel), ld_(ld), comm_(comm),
       cfg_(cfg) {
     validate_params(cfg_);
+    if (bf16_ && f16_)
+        throw std::invalid_argument("MultiFrameEngine: rtm_f16 and rtm_bf16 are exclusive (one storage format per shard)");
+    if (f16_ && !sparse && !cfg_.row_scale)
+        throw std::invalid_argument("MultiFrameEngine: an f16 shard needs its row scales (EngineConfig::row_scale)");
     if (sparse) {
-        if (bf16_) throw std::invalid_argument("MultiFrameEngine: a sparse shard holds fp32 values");
+        if (bf16_ || f16_) throw std::invalid_argument("MultiFrameEngine: a sparse shard holds fp32 values");
         if (!sparse->row_ptr || !sparse->col_ptr)
             throw std::invalid_argument("MultiFrameEngine: sparse shard needs its CSR and CSC arrays");
         sparse_ = true;
@@ -53,7 +57,7 @@ MultiFrameEngine::MultiFrameEngine(int device, const void* A, int64_t nrows, int
         throw std::invalid_argument("MultiFrameEngine: ld and nrows_pad must be multiples of 64 covering the shard");
     cfg_.check_interval = std::max(1, cfg_.check_interval);
     nf_ = batch_width(cfg_.mf_frames);
-    if (!bf16_) {
+    if (!bf16_ && !f16_) {
         int m = cfg_.mf_split_a;
         if (m < 0) {
             const char* e = std::getenv("SART_MF_X3");
@@ -69,9 +73,9 @@ MultiFrameEngine::MultiFrameEngine(int device, const void* A, int64_t nrows, int
     if (const char* e = std::getenv("SART_MF_FWD16"); x3_) fwd16_ = !(e && *e && std::atoi(e) == 0);
     // 128 columns (8 MFMA column groups) exist for bf16 storage and for split-A with the f16-pair back-projection;
     // the fp32 MFMA and three-piece bf16 back-projection paths take 64-frame batches
-    if (nf_ == 128 && !(sparse_ || bf16_ || (x3_ && h16_))) nf_ = 64;
+    if (nf_ == 128 && !(sparse_ || bf16_ || f16_ || (x3_ && h16_))) nf_ = 64;
     const int NF = nf_;
-    split_ = bf16_ || x3_;
+    split_ = bf16_ || f16_ || x3_;
     if (split_) {  // X planes blocked [ld / 32][nf][32] for the forward (SART_MF_XBLK=0: frame-major, A/B runs)
         const char* e = std::getenv("SART_MF_XBLK");
         xblk_ = !(e && *e && std::atoi(e) == 0);
@@ -96,7 +100,7 @@ MultiFrameEngine::MultiFrameEngine(int device, const void* A, int64_t nrows, int
     {  // sweeps per chunk: ~1.5 ms of estimated sweep time (dense: two reads of A at ~5 TB/s; sparse: two gathers over
        // the entries; plus ~13 launches), at least min(check_interval, 4): the host's per-chunk work (snapshot,
        // drain, staging) must hide behind the chunk in flight when sweeps are short (sparse shards)
-        const double bytes = sparse ? 2.0 * (double)sparse->nnz * 8.0 : 2.0 * (double)Pp_ * ld_ * (bf16_ ? 2 : 4);
+        const double bytes = sparse ? 2.0 * (double)sparse->nnz * 8.0 : 2.0 * (double)Pp_ * ld_ * ((bf16_ || f16_) ? 2 : 4);
         const double t_sweep = bytes / 5e12 + 13 * 4e-6;
         chunk_ = (int)std::min<double>(32, std::max<double>(std::min(cfg_.check_interval, 4), std::ceil(1.5e-3 / t_sweep)));
     }
@@ -137,7 +141,7 @@ MultiFrameEngine::MultiFrameEngine(int device, const void* A, int64_t nrows, int
         // the launch plans of the two projections: the knobs are read here, once; buffer sizes, the chunk alignment
         // and every launch come from these two objects
         const MfKnobs knobs = MfKnobs::from_env();
-        const MfPath base = bf16_ ? MfPath::b16 : (x3_ ? MfPath::x3 : MfPath::fp32);
+        const MfPath base = f16_ ? MfPath::s16 : (bf16_ ? MfPath::b16 : (x3_ ? MfPath::x3 : MfPath::fp32));
         fplan_ = mf_plan_forward(fwd16_ ? MfPath::h16 : base, NF, ld_, Pp_, knobs);
         bplan_ = mf_plan_backproject(h16_ ? MfPath::h16 : base, NF, ld_, P_, knobs);
         nsf_ = fplan_.nsplit;
@@ -179,7 +183,16 @@ MultiFrameEngine::MultiFrameEngine(int device, const void* A, int64_t nrows, int
             xmax_.resize(NF);
             launch_mf_row_scales(static_cast<const float*>(A_), ld_, Pp_, rsc_.get(), stream_);
         }
-        if (!h16_) {
+        if (f16_) {
+            // row-scaled f16 storage: f16 pieces of X s_f and of (W / s_p) s_f as on the f16-pair split-A path, but no
+            // scales of A to compute: the rows' come with the shard (cfg_.row_scale), columns need none
+            W16_.resize((size_t)2 * NF * Pp_);
+            Ws_.resize((size_t)Pp_ * NF);
+            wmax_.resize(NF);
+            wscale_.resize(NF);
+            xinv_.resize(NF);
+            xmax_.resize(NF);
+        } else if (!h16_) {
             Wh_.resize((size_t)(x3_ ? 2 : 1) * NF * Pp_);  // split-A: hi and mid planes
             Wl_.resize((size_t)NF * Pp_);
         }
@@ -187,7 +200,7 @@ MultiFrameEngine::MultiFrameEngine(int device, const void* A, int64_t nrows, int
     if (sparse_)
         rs_.compute_sparse(sp_, P_, Pp_, V_, ld_, comm_, cfg_, stream_);
     else
-        rs_.compute(A_, P_, Pp_, V_, ld_, comm_, cfg_, stream_, false, bf16_);
+        rs_.compute(A_, P_, Pp_, V_, ld_, comm_, cfg_, stream_, false, bf16_, f16_ ? cfg_.row_scale + Pp_ : nullptr);
     // chunks of the overlapped back-projection / all-reduce pipeline (several ranks only): SART_MF_CHUNKS
     // (default 4) voxel ranges aligned to the back-projection's voxel tile, each >= 1 MiB of corrections
     int nchunks = 1;
@@ -258,11 +271,13 @@ void MultiFrameEngine::set_laplacian(const int64_t* row_ptr, const int32_t* col,
 
 std::string MultiFrameEngine::forward_split() const {
     if (sparse_) return "sparse-fp32";
+    if (f16_) return "f16-storage";
     return bf16_ ? "bf16-storage" : (!x3_ ? "fp32" : (fwd16_ ? "f16x2" : "bf16x2"));
 }
 
 std::string MultiFrameEngine::backproject_split() const {
     if (sparse_) return "sparse-fp32";
+    if (f16_) return "f16-storage";
     return bf16_ ? "bf16-storage" : (!x3_ ? "fp32" : (h16_ ? "f16x2" : "bf16x3"));
 }
 
@@ -277,6 +292,14 @@ void MultiFrameEngine::forward() {
         launch_mf_split_x16(X_.get(), ld_, nf_, x1, x2, xmax_.get(), xinv_.get(), stream_, true, xblk_);
         launch_mf_forward_h16(fplan_, static_cast<const float*>(A_), P_, x1, x2, Fs_.get(), stream_, xblk_, rsc_.get(),
                               xinv_.get());
+        return;
+    }
+    if (f16_) {  // f16 pieces of X s_f in the bf16 planes' layout (no k permutation)
+        uint16_t* x1 = reinterpret_cast<uint16_t*>(Xh_.get());
+        uint16_t* x2 = reinterpret_cast<uint16_t*>(Xl_.get());
+        launch_mf_split_x16(X_.get(), ld_, nf_, x1, x2, xmax_.get(), xinv_.get(), stream_, false, xblk_);
+        launch_mf_forward_s16(fplan_, static_cast<const f16s_t*>(A_), P_, x1, x2, Fs_.get(), stream_, xblk_,
+                              cfg_.row_scale, xinv_.get());
         return;
     }
     if (split_) {
@@ -305,7 +328,17 @@ void MultiFrameEngine::backproject(const float* W, bool split_w, int64_t v0, int
                                      v1, stream_, g_mf_skip);
         return;
     }
-    if (h16_) {
+    if (f16_) {
+        // the kernel multiplies by A s_p: the rows' 1 / s_p goes into W before its per-frame f16 split
+        uint16_t* w1 = W16_.get();
+        uint16_t* w2 = W16_.get() + (size_t)nf_ * Pp_;
+        if (split_w) {
+            launch_mf_scale_w_rows(W, cfg_.row_scale + Pp_, Pp_, nf_, Ws_.get(), stream_);
+            launch_mf_split_w16(Ws_.get(), Pp_, nf_, Pp_, w1, w2, wmax_.get(), 1.f, wscale_.get(), stream_, false);
+        }
+        launch_mf_backproject_s16(bplan_, static_cast<const f16s_t*>(A_), w1, w2, Pp_, part_.get(), stream_, v0, v1,
+                                  wscale_.get());
+    } else if (h16_) {
         uint16_t* w1 = W16_.get();
         uint16_t* w2 = W16_.get() + (size_t)nf_ * Pp_;
         if (split_w)

@@ -26,7 +26,8 @@ namespace sart {
 
 class MultiFrameEngine {
    public:
-    // A: fp32 [nrows_pad][ld], or bf16 when cfg.rtm_bf16 (bf16 MFMA projections, multiframe_bf16.hip); fp32
+    // A: fp32 [nrows_pad][ld], or bf16 when cfg.rtm_bf16 (bf16 MFMA projections, multiframe_bf16.hip), or row-scaled
+    // f16 when cfg.rtm_f16 (cfg.row_scale; the same kernels on the f16 MFMA, "f16-storage"); fp32
     // shards run on fp32 MFMA (multiframe.hip) or split into bf16 on the bf16 matrix cores (cfg.mf_split_a)
     // sparse: the shard as device CSR + CSC arrays instead (A null; not owned): fp32 SpMM projections on the
     // frames' fp32 state (csrc/kernels/sparse.hip), no operand splits
@@ -119,6 +120,10 @@ class MultiFrameEngine {
     DeviceArray<float> Wt_;  // sparse: W as frame-order planes [nf / PW][rows][PW] (launch_mf_w_planes)
     int pw_ = 64;            // sparse: frames per SpMM plane (mf_sparse_plane_width, fixed at construction)
     bool bf16_ = false;
+    // row-scaled f16 storage (EngineConfig::rtm_f16, MfPath::s16): the bf16-storage kernels on the f16 MFMA; X / W
+    // pieces as on the f16-pair path (Xh_ / Xl_, W16_, xinv_, wscale_), W with the rows' 1 / s_p folded in (Ws_)
+    bool f16_ = false;
+    DeviceArray<float> Ws_;
     bool x3_ = false;     // fp32 shard on the bf16 matrix cores (EngineConfig::mf_split_a)
     bool split_ = false;  // X / W enter as hi + lo bf16 planes (bf16_ || x3_)
     bool xblk_ = false;   // X planes blocked [ld / 32][nf][32] (launch_mf_split_x / forward xblk)

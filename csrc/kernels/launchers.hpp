@@ -28,6 +28,28 @@ void launch_backproject(const bf16_t* A, int64_t ld, int64_t nrows, const float*
                         const SartState* st, hipStream_t stream);
 void launch_colsum_f64(const float* A, int64_t ld, int64_t nrows, int nsplit, double* partial, hipStream_t stream);
 void launch_colsum_f64(const bf16_t* A, int64_t ld, int64_t nrows, int nsplit, double* partial, hipStream_t stream);
+// Row-scaled f16 storage (f16s_t, sart_common.hpp): A holds f16 bits of A s_p, rinv[p] = 1 / s_p (the second half of
+// the shard's scale array rsc: [nrows_pad] scales, then [nrows_pad] inverses). The forward writes f = rinv dot(H, x)
+// and, for the back-projection (which meets H again), the weight rinv a (ghat - f) / rinv a f; ||f||^2 is taken
+// from f. The back-projection's w must carry rinv (launch_scale_rows for operands made elsewhere). Row sums are
+// rinv sum H, column sums sum_p H[p][v] rinv[p], both exact products in fp64.
+void launch_forward(int epi, const f16s_t* A, int64_t ld, int64_t nrows, int64_t nrows_pad, const float* x,
+                    const float* ghat, const float* arow, float* out_f, float* out_w, double* Fpart,
+                    const SartState* st, hipStream_t stream, const float* rinv);
+void launch_rowsum_f64(const f16s_t* A, int64_t ld, int64_t nrows, double* out, hipStream_t stream,
+                       const float* rinv);
+void launch_backproject(const f16s_t* A, int64_t ld, int64_t nrows, const float* w, int nsplit, float* partial,
+                        const SartState* st, hipStream_t stream);
+void launch_colsum_f64(const f16s_t* A, int64_t ld, int64_t nrows, int nsplit, double* partial, hipStream_t stream,
+                       const float* rinv);
+// One launch: a device fp32 block of whole rows [n][ld] -> its f16 bits (dst [n][ld]; columns >= nvoxel zero) and
+// its scales (scale[i] = s_p, inv_scale[i] = 1 / s_p for i < n). counts (optional, two device words per shard):
+// counts[0] += the non-zero finite inputs stored as zero or as an f16 subnormal, counts[1] += the non-zero finite
+// inputs. utils/f16rows.py is the NumPy definition.
+void launch_f32_to_f16_rows(const float* src, int64_t n, int64_t ld, int64_t nvoxel, f16s_t* dst, float* scale,
+                            float* inv_scale, unsigned long long* counts, hipStream_t stream);
+// v[i] *= rinv[i] for i < n
+void launch_scale_rows(float* v, const float* rinv, int64_t n, hipStream_t stream);
 // sparse.hip: a sparse RTM shard held twice on the device, as CSR (rows: the forward projection and the row sums) and
 // CSC (columns: the back-projection and the column sums), so both projections are gathers with one writer per output
 // (no atomics: bitwise reproducible). Indices are 32-bit column / row numbers, offsets 64-bit.
@@ -274,6 +296,18 @@ void launch_mf_split_x16(const float* X, int64_t ld, int nf, uint16_t* x1, uint1
 // output scaled by 1 / (s_p s_f)
 void launch_mf_forward_h16(const MfFwdPlan& p, const float* A, int64_t nrows, const uint16_t* X1, const uint16_t* X2,
                            float* Fout, hipStream_t stream, bool xblk, const float* rsc, const float* xinv);
+// Row-scaled f16 storage (MfPath::s16): the bf16-storage kernels on v_mfma_f32_16x16x32_f16. A holds f16 bits of
+// A s_p (rsc: the shard's [nrows_pad] scales, then their inverses); X1 / X2 from launch_mf_split_x16 with perm false
+// (blocked when xblk), W1 / W2 from launch_mf_split_w16 (a_scale 1) of launch_mf_scale_w_rows' output; two products
+// per element; the forward's output is scaled by 1 / (s_p s_f), the back-projection's by inv_scale[f]
+void launch_mf_forward_s16(const MfFwdPlan& p, const f16s_t* A, int64_t nrows, const uint16_t* X1, const uint16_t* X2,
+                           float* Fout, hipStream_t stream, bool xblk, const float* rsc, const float* xinv);
+void launch_mf_backproject_s16(const MfBwdPlan& p, const f16s_t* A, const uint16_t* W1, const uint16_t* W2,
+                               int64_t ldw, float* partial, hipStream_t stream, int64_t v0, int64_t v1,
+                               const float* inv_scale);
+// out[p][s] = W[p][s] rinv[p] for W [nrows_pad][nf] (the rows' 1 / s_p folded into the back-projection operand)
+void launch_mf_scale_w_rows(const float* W, const float* rinv, int64_t nrows_pad, int nf, float* out,
+                            hipStream_t stream);
 // three: hi [nf][ldw] then mid [nf][ldw] in `hi` (2 nf ldw elements), lo: the split-A back-projection's planes
 void launch_mf_split_w(const float* W, int64_t nrows_pad, int nf, int64_t ldw, bf16_t* hi, bf16_t* lo,
                        hipStream_t stream, bool three = false);

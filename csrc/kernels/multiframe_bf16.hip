@@ -37,6 +37,14 @@
 // combined weight >= 2^-16). Three / six bf16 MFMAs cost 3/16 / 6/16 of one fp32 MFMA of the same K; the splits
 // are 3 / 5 VALU operations per element of A, which overlap the stream. The stored matrix, the fp32 state and the
 // fp32 sums are those of the fp32 engine.
+//
+// Row-scaled f16 storage (AT = f16s_t, MfPath::s16: --rtm_f16). The bf16-storage LDS kernels instantiated for f16
+// tiles: A holds f16 bits of A s_p (a power-of-two scale per row, sart_common.hpp), loaded, staged and regrouped as
+// bf16 tiles are (two bytes per element), multiplied on v_mfma_f32_16x16x32_f16 with the two f16 pieces of X s_f
+// (forward) / (W / s_p) s_f (back-projection) that the f16-pair split-A path uses, two products per element: A is
+// exact in the operand and each product is within ~2^-22, with none of split-A's register splits. The epilogues
+// multiply by 1 / (s_p s_f) and 1 / s_f, exactly. Only the planner's default variants are instantiated
+// (MF_FWD_S16_VARIANTS / MF_BWD_S16_VARIANTS); the bf16 / split-A instantiations are unchanged.
 #include "sart_common.hpp"
 #include "launchers.hpp"
 #include "../engine/mf_variants.hpp"
@@ -100,6 +108,17 @@ __device__ __forceinline__ floatx4 mfma_h16(const u32x4 a, const u32x4 b, floatx
     return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(halfx8_t, a), __builtin_bit_cast(halfx8_t, b),
                                                   c, 0, 0, 0);
 }
+__device__ __forceinline__ floatx4 mfma_h16(const uint4 a, const u32x4 b, floatx4 c) {
+    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(halfx8_t, a), __builtin_bit_cast(halfx8_t, b),
+                                                  c, 0, 0, 0);
+}
+// The 16-bit-storage kernels' product: bf16 storage on v_mfma_f32_16x16x32_bf16, row-scaled f16 storage (F16) on
+// v_mfma_f32_16x16x32_f16; same fragment maps, so one kernel body serves both
+template <bool F16, typename TA, typename TB>
+__device__ __forceinline__ floatx4 mfma_16(const TA a, const TB b, floatx4 c) {
+    if constexpr (F16) return mfma_h16(a, b, c);
+    else return mfma_b16(a, b, c);
+}
 // Two VALU operations per element: p1 = rne16(a s) and p2 = rne16(a s - p1) are each one v_fma_mix{lo,hi}_f16 (fp32
 // a and s, for p2 an f16 half of p1 as the negated addend; the f16 result goes into one half of the packed register).
 // a s is exact (s is a power of two inside the clamped range) and so is a s - p1 in fp32, so each single rounding to
@@ -162,6 +181,19 @@ __device__ __forceinline__ void split_phase3(const u32x4 (&v)[8], u32x4& hi, u32
 template <typename AT> struct ARaw;
 template <> struct ARaw<bf16_t> { typedef uint4 fwd; typedef uint2 bwd; };
 template <> struct ARaw<float> { typedef u32x8 fwd; typedef u32x4 bwd; };
+template <> struct ARaw<f16s_t> { typedef uint4 fwd; typedef uint2 bwd; };
+
+// Last argument of k_mf_backproject_b16_lds: the skip flag; f16 storage also passes the frames' inverse scales of the
+// W pieces (launch_mf_split_w16) for its epilogue. A type of the storage, so the bf16 / split-A instantiations keep
+// their signature.
+struct BwdTailS16 {
+    const int* skip;
+    const float* inv_scale;
+};
+template <typename AT> struct BwdTail { typedef const int* __restrict__ type; };
+template <> struct BwdTail<f16s_t> { typedef BwdTailS16 type; };
+__device__ __forceinline__ const int* tail_skip(const int* t) { return t; }
+__device__ __forceinline__ const int* tail_skip(const BwdTailS16& t) { return t.skip; }
 
 // Fragment of voxel phase P from the eight 8-byte row loads: element j = bf16 P of row load j.
 template <int P>
@@ -346,6 +378,11 @@ __global__ __launch_bounds__(256, (mf_fwd_min_waves<AT, NG>())) void k_mf_forwar
     const int64_t c1 = (c0 + cols_per_split < ld) ? c0 + cols_per_split : ld;
     Fout += (int64_t)blockIdx.y * nrows_pad * NF;
     constexpr bool A32 = std::is_same<AT, float>::value;
+    // S16: row-scaled f16 storage (f16s_t). The bf16-storage kernel on v_mfma_f32_16x16x32_f16: A's tiles are loaded,
+    // staged and regrouped as bf16 ones (same two bytes per element), X enters as the two f16 pieces of X s_f
+    // (launch_mf_split_x16, the bf16 planes' layouts), two products per element (A x1 + A x2: A is exact in the
+    // operand, 2^-22 per product), and the epilogue multiplies by 1 / (s_p s_f) like H16 (FwdCols::rsc / xinv)
+    constexpr bool S16 = std::is_same<AT, f16s_t>::value;
     constexpr bool LATE = SART_MF_STAGE_LATE && A32;  // stage_next after the MFMAs (split-A only, see below)
     constexpr bool NT_AS = SART_MF_AS_NT != 0;
     // split-A: lane (r, g) loads voxels 4 g .. 4 g + 3 and 16 + 4 g .. of each 32-voxel block (two contiguous
@@ -507,8 +544,8 @@ __global__ __launch_bounds__(256, (mf_fwd_min_waves<AT, NG>())) void k_mf_forwar
                     for (int j = 0; j < NG; ++j)
 #pragma unroll
                         for (int rt = 0; rt < RT; ++rt) {
-                            acc[rt][j] = mfma_b16(a[sl][rt][kb], xf[kb][0][j], acc[rt][j]);
-                            acc[rt][j] = mfma_b16(a[sl][rt][kb], xf[kb][1][j], acc[rt][j]);
+                            acc[rt][j] = mfma_16<S16>(a[sl][rt][kb], xf[kb][0][j], acc[rt][j]);
+                            acc[rt][j] = mfma_16<S16>(a[sl][rt][kb], xf[kb][1][j], acc[rt][j]);
                         }
                 if constexpr (LATE) stage_next();
                 __syncthreads();
@@ -564,8 +601,8 @@ __global__ __launch_bounds__(256, (mf_fwd_min_waves<AT, NG>())) void k_mf_forwar
                         const u32x4 xl = xs[((kb * 2 + 1) * NG + j) * 64];
 #pragma unroll
                         for (int rt = 0; rt < RT; ++rt) {
-                            acc[rt][j] = mfma_b16(af[rt], xh, acc[rt][j]);
-                            acc[rt][j] = mfma_b16(af[rt], xl, acc[rt][j]);
+                            acc[rt][j] = mfma_16<S16>(af[rt], xh, acc[rt][j]);
+                            acc[rt][j] = mfma_16<S16>(af[rt], xl, acc[rt][j]);
                         }
                     }
                 } else {
@@ -575,8 +612,8 @@ __global__ __launch_bounds__(256, (mf_fwd_min_waves<AT, NG>())) void k_mf_forwar
                         const u32x4 xl = xs[((kb * 2 + 1) * NG + j) * 64];
 #pragma unroll
                         for (int rt = 0; rt < RT; ++rt) {
-                            acc[rt][j] = mfma_b16(a[sl][rt][kb], xh, acc[rt][j]);
-                            acc[rt][j] = mfma_b16(a[sl][rt][kb], xl, acc[rt][j]);
+                            acc[rt][j] = mfma_16<S16>(a[sl][rt][kb], xh, acc[rt][j]);
+                            acc[rt][j] = mfma_16<S16>(a[sl][rt][kb], xl, acc[rt][j]);
                         }
                     }
                 }
@@ -607,7 +644,7 @@ __global__ __launch_bounds__(256, (mf_fwd_min_waves<AT, NG>())) void k_mf_forwar
             else acc[t][j] = sum[t][j] + acc[t][j];
         }
     if (!live) return;
-    if constexpr (H16) {  // 1 / (s_p s_f), exact (powers of two)
+    if constexpr (H16 || S16) {  // 1 / (s_p s_f), exact (powers of two)
 #pragma unroll
         for (int j = 0; j < NG; ++j) {
             const float xi = fc.xinv[16 * j + r];
@@ -738,11 +775,17 @@ __global__ __launch_bounds__(256, (NG == 4 ? mf_bwd_min_waves<AT, VT>() : (std::
                                                                 int64_t nrows32, const bf16_t* __restrict__ Wh,
                                                                 const bf16_t* __restrict__ Wl, int64_t ldw,
                                                                 int64_t rows_per_split, float* __restrict__ partial,
-                                                                int64_t vb0, int64_t vend, const int* __restrict__ skip) {
+                                                                int64_t vb0, int64_t vend,
+                                                                typename BwdTail<AT>::type tail) {
+    const int* skip = tail_skip(tail);
     if (skip && *skip) return;
     constexpr int NF = 16 * NG;
     constexpr int RS = DEPTH + 1;
     constexpr bool A32 = std::is_same<AT, float>::value;
+    // S16: row-scaled f16 storage on v_mfma_f32_16x16x32_f16 (see k_mf_forward_b16_lds): W enters as the two f16
+    // pieces of (W / s_p) s_f (launch_mf_scale_w_rows, launch_mf_split_w16) in the bf16 planes' layout, two products
+    // per element, the epilogue multiplies by the frames' 1 / s_f (BwdTailS16::inv_scale)
+    constexpr bool S16 = std::is_same<AT, f16s_t>::value;
     constexpr bool LATE = SART_MF_STAGE_LATE && A32;  // stage_next after the MFMAs (split-A only)
     constexpr int NPL = A32 ? 3 : 2;              // W planes: hi, (mid,) lo
     constexpr int C = NPL * NG;                   // 1 KiB W pieces per step
@@ -845,8 +888,8 @@ __global__ __launch_bounds__(256, (NG == 4 ? mf_bwd_min_waves<AT, VT>() : (std::
                     for (int j = 0; j < NG; ++j)
 #pragma unroll
                         for (int p = 0; p < 4; ++p) {
-                            acc[vt][p][j] = mfma_b16(fr[p], wf[0][j], acc[vt][p][j]);
-                            acc[vt][p][j] = mfma_b16(fr[p], wf[1][j], acc[vt][p][j]);
+                            acc[vt][p][j] = mfma_16<S16>(fr[p], wf[0][j], acc[vt][p][j]);
+                            acc[vt][p][j] = mfma_16<S16>(fr[p], wf[1][j], acc[vt][p][j]);
                         }
                 }
                 if constexpr (LATE) stage_next();
@@ -891,8 +934,8 @@ __global__ __launch_bounds__(256, (NG == 4 ? mf_bwd_min_waves<AT, VT>() : (std::
                         const u32x4 wh = ws[j * 64], wl = ws[(NG + j) * 64];
 #pragma unroll
                         for (int p = 0; p < 4; ++p) {
-                            acc[vt][p][j] = mfma_b16(fr[p], wh, acc[vt][p][j]);
-                            acc[vt][p][j] = mfma_b16(fr[p], wl, acc[vt][p][j]);
+                            acc[vt][p][j] = mfma_16<S16>(fr[p], wh, acc[vt][p][j]);
+                            acc[vt][p][j] = mfma_16<S16>(fr[p], wl, acc[vt][p][j]);
                         }
                     }
                 }
@@ -908,6 +951,22 @@ __global__ __launch_bounds__(256, (NG == 4 ? mf_bwd_min_waves<AT, VT>() : (std::
     }
     if (!live) return;
     float* out = partial + (int64_t)blockIdx.y * ld * NF;
+    if constexpr (S16) {  // 1 / s_f, exact (powers of two)
+        float isc[NG];
+#pragma unroll
+        for (int j = 0; j < NG; ++j) isc[j] = tail.inv_scale[16 * j + i16];
+#pragma unroll
+        for (int vt = 0; vt < VT; ++vt)
+#pragma unroll
+            for (int p = 0; p < 4; ++p)
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const int64_t v = (vb + vt) * 64 + 4 * (g * 4 + q) + p;
+#pragma unroll
+                    for (int j = 0; j < NG; ++j) out[v * NF + 16 * j + i16] = acc[vt][p][j][q] * isc[j];
+                }
+        return;
+    }
 #pragma unroll
     for (int vt = 0; vt < VT; ++vt)
 #pragma unroll
@@ -1100,6 +1159,10 @@ typedef void (*BwdB16Fn)(const bf16_t*, int64_t, int64_t, const bf16_t*, const b
                          int64_t, int64_t, const int*);
 typedef void (*BwdX3Fn)(const float*, int64_t, int64_t, const bf16_t*, const bf16_t*, int64_t, int64_t, float*, int64_t,
                         int64_t, const int*);
+typedef void (*FwdS16Fn)(const f16s_t*, int64_t, int64_t, int64_t, const bf16_t*, const bf16_t*, float*, FwdCols,
+                         const int*);
+typedef void (*BwdS16Fn)(const f16s_t*, int64_t, int64_t, const bf16_t*, const bf16_t*, int64_t, int64_t, float*,
+                         int64_t, int64_t, BwdTailS16);
 typedef void (*BwdH16Fn)(const float*, int64_t, int64_t, const uint16_t*, const uint16_t*, int64_t, int64_t, float*,
                          int64_t, int64_t, const float*, const float*, const int*);
 
@@ -1139,6 +1202,18 @@ const MfVariant<BwdX3Fn> kBwdX3[] = {
 const MfVariant<BwdH16Fn> kBwdH16[] = {
 #define X(NG, D, EW, MW) {mf_key_bwd_h16(NG, D, EW, MW), k_mf_backproject_h16<NG, D, EW, MW>},
     MF_BWD_H16_VARIANTS(X)
+#undef X
+};
+
+const MfVariant<FwdS16Fn> kFwdS16[] = {
+#define X(NG, D, RT, KB, AS, EX) \
+    {mf_key_fwd_s16(NG, D, RT, KB, AS, EX), k_mf_forward_b16_lds<NG, D, RT, KB, f16s_t, AS, EX>},
+    MF_FWD_S16_VARIANTS(X)
+#undef X
+};
+const MfVariant<BwdS16Fn> kBwdS16[] = {
+#define X(NG, D, VT, EW) {mf_key_bwd_s16(NG, D, VT, EW), k_mf_backproject_b16_lds<NG, D, VT, f16s_t, EW>},
+    MF_BWD_S16_VARIANTS(X)
 #undef X
 };
 
@@ -1190,6 +1265,28 @@ void launch_mf_forward_h16(const MfFwdPlan& p, const float* A, int64_t nrows, co
     check_plan(p.key, MfPath::h16, true, "mf_forward_h16");
     if (!rsc || !xinv) throw std::runtime_error("mf_forward_h16: row scales and frame scales required");
     forward_split(kFwdA32, "k_mf_forward_h16", p, A, nrows, X1, X2, Fout, stream, xblk, rsc, xinv);
+}
+
+// Row-scaled f16 storage: X1 / X2 from launch_mf_split_x16 without perm (blocked when xblk), rsc the shard's row
+// scales, xinv the frames' inverse scales
+void launch_mf_forward_s16(const MfFwdPlan& p, const f16s_t* A, int64_t nrows, const uint16_t* X1, const uint16_t* X2,
+                           float* Fout, hipStream_t stream, bool xblk, const float* rsc, const float* xinv) {
+    check_plan(p.key, MfPath::s16, true, "mf_forward_s16");
+    if (!rsc || !xinv) throw std::runtime_error("mf_forward_s16: row scales and frame scales required");
+    forward_split(kFwdS16, "k_mf_forward_s16", p, A, nrows, X1, X2, Fout, stream, xblk, rsc, xinv);
+}
+
+// W1 / W2: launch_mf_split_w16 of W with the rows' 1 / s_p folded in (launch_mf_scale_w_rows), inv_scale its output
+void launch_mf_backproject_s16(const MfBwdPlan& p, const f16s_t* A, const uint16_t* W1, const uint16_t* W2,
+                               int64_t ldw, float* partial, hipStream_t stream, int64_t v0, int64_t v1,
+                               const float* inv_scale) {
+    check_plan(p.key, MfPath::s16, false, "mf_backproject_s16");
+    if (!inv_scale) throw std::runtime_error("mf_backproject_s16: frame scales required");
+    const int64_t vw0 = wave_tiles(p, ldw, v0, v1, "mf_backproject_s16");
+    hipLaunchKernelGGL(mf_variant(kBwdS16, p.key, "mf_backproject_s16"), dim3(p.grid_x(v0, v1), (unsigned)p.nsplit),
+                       dim3(256), 0, stream, A, p.ld, (p.nrows + 31) / 32 * 32, W1, W2, ldw, p.rps, partial, vw0, v1,
+                       BwdTailS16{g_mf_skip, inv_scale});
+    check_launch("k_mf_backproject_s16");
 }
 
 void launch_mf_backproject_b16(const MfBwdPlan& p, const bf16_t* A, const bf16_t* Wh, const bf16_t* Wl, int64_t ldw,

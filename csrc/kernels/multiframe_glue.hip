@@ -965,12 +965,7 @@ __device__ __forceinline__ int mf_w16_exp(unsigned mbits) {  // e with max |w| =
     (void)frexpf(__uint_as_float(mbits), &e);
     return e;
 }
-// The f16 scale exponent 14 - e of a maximum m 2^e, clamped so that the scale and its inverse are both normal
-// floats (a maximum below 2^-106 would otherwise give an infinite scale, and w * inf non-finite pieces)
-__device__ __host__ __forceinline__ int mf_f16_shift(int e) {
-    const int s = 14 - e;
-    return s > 120 ? 120 : (s < -120 ? -120 : s);
-}
+// (the f16 scale exponent of a maximum m 2^e: mf_f16_shift, sart_common.hpp)
 
 template <int TN>
 __global__ __launch_bounds__(256) void k_mf_split_w16(const float* __restrict__ W, int64_t nrows_pad, int nf,
@@ -1147,6 +1142,32 @@ __global__ __launch_bounds__(256) void k_mf_split_x16(const float* __restrict__ 
     if (perm) o = (o & ~(int64_t)7) | ((o & 3) << 1) | ((o >> 2) & 1);
     reinterpret_cast<uint2*>(x1)[o] = make_uint2(h[0] | (unsigned)h[1] << 16, h[2] | (unsigned)h[3] << 16);
     reinterpret_cast<uint2*>(x2)[o] = make_uint2(l[0] | (unsigned)l[1] << 16, l[2] | (unsigned)l[3] << 16);
+}
+
+// out[p][s] = W[p][s] rinv[p] (W [nrows_pad][nf] in any slot order): the back-projection operand of a row-scaled f16
+// shard, whose kernel multiplies by A s_p; before the per-frame f16 split, whose scales then see the folded values
+__global__ __launch_bounds__(256) void k_mf_scale_w_rows(const float* __restrict__ W, const float* __restrict__ rinv,
+                                                         int64_t n4, int nf4, float* __restrict__ out,
+                                                         const int* __restrict__ skip) {
+    if (skip && *skip) return;
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n4) return;
+    const float r = rinv[i / nf4];
+    float4 v = reinterpret_cast<const float4*>(W)[i];
+    v.x *= r;
+    v.y *= r;
+    v.z *= r;
+    v.w *= r;
+    reinterpret_cast<float4*>(out)[i] = v;
+}
+
+void launch_mf_scale_w_rows(const float* W, const float* rinv, int64_t nrows_pad, int nf, float* out,
+                            hipStream_t stream) {
+    check_nf(nf, "mf_scale_w_rows");
+    const int64_t n4 = nrows_pad * nf / 4;
+    if (n4 <= 0) return;
+    hipLaunchKernelGGL(k_mf_scale_w_rows, dim3(nb(n4)), dim3(256), 0, stream, W, rinv, n4, nf / 4, out, g_mf_skip);
+    check_launch("k_mf_scale_w_rows");
 }
 
 void launch_mf_row_scales(const float* A, int64_t ld, int64_t nrows_pad, float* rsc, hipStream_t stream) {

@@ -11,9 +11,10 @@
 //   * ray density / ray length computed on the CPU in fp64 (reference sartsolver.cpp:38-56) ->
 //     k_colsum_f64 / k_rowsum_f64 on the device with fp64 accumulation.
 //
-// All loads are 16 B per lane (4 fp32 or 8 bf16 columns); one wave instruction moves 1 KiB of a row. The
-// kernels are templated on the RTM storage type (RtmVec, sart_common.hpp): fp32, or bf16 storage with fp32
-// products and sums (opt-in, half the bytes per sweep).
+// All loads are 16 B per lane (4 fp32 or 8 bf16 / f16 columns); one wave instruction moves 1 KiB of a row. The
+// kernels are templated on the RTM storage type (RtmVec, sart_common.hpp): fp32, or bf16 / row-scaled f16 storage
+// with fp32 products and sums (opt-in, half the bytes per sweep). Row-scaled f16 (f16s_t) stores A s_p with a
+// power-of-two s_p per row: the kernels take the inverse scales (rinv[p] = 1 / s_p) and apply them exactly.
 #include "sart_common.hpp"
 
 #include <stdexcept>
@@ -50,7 +51,8 @@ __global__ __launch_bounds__(256) void k_forward(const AT* __restrict__ A, int64
                                                  float* __restrict__ out_f,
                                                  float* __restrict__ out_w,
                                                  double* __restrict__ Fpart,
-                                                 const SartState* __restrict__ st) {
+                                                 const SartState* __restrict__ st,
+                                                 const float* __restrict__ rinv) {
     if (st != nullptr && st->done) return;
     __shared__ float red[4][RPB];
 
@@ -92,11 +94,18 @@ __global__ __launch_bounds__(256) void k_forward(const AT* __restrict__ A, int64
         double f2 = 0.0;
         if (tid < RPB) {
             const int64_t row = row0 + tid;
-            const float f = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
+            float f = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
             if (row < nrows) {
+                // row-scaled f16 storage: the dot ran over A s_p; f and the back-projection's weight (which meets
+                // A s_p again) take the row's 1 / s_p, a power of two
+                float ri = 1.f;
+                if constexpr (L::kRowScaled) {
+                    ri = rinv[row];
+                    f *= ri;
+                }
                 if (out_f) out_f[row] = f;
-                if (EPI == kEpiLinear) out_w[row] = arow[row] * (ghat[row] - f);
-                if (EPI == kEpiLog) out_w[row] = arow[row] * f;
+                if (EPI == kEpiLinear) out_w[row] = ri * (arow[row] * (ghat[row] - f));
+                if (EPI == kEpiLog) out_w[row] = ri * (arow[row] * f);
                 f2 = (double)f * (double)f;
             }
         }
@@ -110,7 +119,8 @@ __global__ __launch_bounds__(256) void k_forward(const AT* __restrict__ A, int64
 // fp64 row sums (ray length, reference sartsolver.cpp:49-56).
 template <typename AT>
 __global__ __launch_bounds__(256) void k_rowsum_f64(const AT* __restrict__ A, int64_t ld, int64_t nrows,
-                                                    double* __restrict__ out) {
+                                                    double* __restrict__ out,
+                                                    const float* __restrict__ rinv) {
     using L = RtmVec<AT>;
     __shared__ double red[4];
     const int tid = threadIdx.x;
@@ -129,7 +139,11 @@ __global__ __launch_bounds__(256) void k_rowsum_f64(const AT* __restrict__ A, in
     acc = wave_sum(acc);
     if ((tid & 63) == 0) red[tid >> 6] = acc;
     __syncthreads();
-    if (tid == 0 && row < nrows) out[row] = ((red[0] + red[1]) + red[2]) + red[3];
+    if (tid == 0 && row < nrows) {
+        double s = ((red[0] + red[1]) + red[2]) + red[3];
+        if constexpr (L::kRowScaled) s *= (double)rinv[row];
+        out[row] = s;
+    }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -196,7 +210,8 @@ __global__ __launch_bounds__(256) void k_backproject(const AT* __restrict__ A, i
 // fp64 column sums (ray density, reference sartsolver.cpp:38-47), same split-K structure.
 template <typename AT>
 __global__ __launch_bounds__(256) void k_colsum_f64(const AT* __restrict__ A, int64_t ld, int64_t nrows,
-                                                    int64_t rows_per_split, double* __restrict__ partial) {
+                                                    int64_t rows_per_split, double* __restrict__ partial,
+                                                    const float* __restrict__ rinv) {
     using L = RtmVec<AT>;
     constexpr int NF4 = L::NF4;
     const int64_t cv = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -211,6 +226,17 @@ __global__ __launch_bounds__(256) void k_colsum_f64(const AT* __restrict__ A, in
     for (int64_t r = r_begin; r < r_end; ++r) {
         float4 av[NF4];
         L::load(A + r * ld, cv, av);
+        if constexpr (L::kRowScaled) {  // H / s_p: exact in fp64
+            const double ri = (double)rinv[r];
+#pragma unroll
+            for (int j = 0; j < NF4; ++j) {
+                s[4 * j + 0] += (double)av[j].x * ri;
+                s[4 * j + 1] += (double)av[j].y * ri;
+                s[4 * j + 2] += (double)av[j].z * ri;
+                s[4 * j + 3] += (double)av[j].w * ri;
+            }
+            continue;
+        }
 #pragma unroll
         for (int j = 0; j < NF4; ++j) {
             s[4 * j + 0] += av[j].x;
@@ -240,6 +266,101 @@ __global__ __launch_bounds__(256) void k_f32_to_bf16(const float* __restrict__ s
         o.y = cvt(v.z) | (cvt(v.w) << 16);
         reinterpret_cast<uint2*>(dst)[i] = o;
     }
+}
+
+// fp32 -> row-scaled f16 (sart_common.hpp, f16s_t): one workgroup per row of a block of whole rows [n][ld]. Pass 1:
+// m = max |a| over the row's finite entries in columns < nvoxel (bit patterns, so the order does not matter) and the
+// scale exponent s = mf_f16_shift(e) for m = mant 2^e (0 for an all-zero row). Pass 2 (the row comes back from L2):
+// h = rne_f16(a 2^s), f16 subnormals kept, NaN stored as the canonical 0x7e00, columns >= nvoxel as zero; 16-byte
+// stores of 8 elements. counts (optional, two words, one pair per shard): counts[0] += the non-zero finite inputs
+// stored as zero or as an f16 subnormal (entries below 2^-27 of their row's maximum), counts[1] += all non-zero finite
+// inputs: the loaders' statistic. mpi_cuda_sartsolver_amd/utils/f16rows.py is
+// the same definition in NumPy; the two agree bit for bit.
+__global__ __launch_bounds__(256) void k_f32_to_f16_rows(const float* __restrict__ src, int64_t ld, int64_t nvoxel,
+                                                         f16s_t* __restrict__ dst, float* __restrict__ scale,
+                                                         float* __restrict__ inv_scale,
+                                                         unsigned long long* __restrict__ counts) {
+    __shared__ unsigned red[4], red2[4];
+    __shared__ int s_shift;
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int64_t row = blockIdx.x;
+    const float* __restrict__ a = src + row * ld;
+    const int64_t nv4 = (nvoxel + 3) / 4;  // <= ld / 4
+    unsigned m = 0u;
+    for (int64_t c = tid; c < nv4; c += 256) {
+        const float4 v = reinterpret_cast<const float4*>(a)[c];
+        const float xs[4] = {fabsf(v.x), fabsf(v.y), fabsf(v.z), fabsf(v.w)};
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (4 * c + k < nvoxel && xs[k] <= 3.0e38f) m = max(m, __float_as_uint(xs[k]));  // finite values only
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, o, kWave));
+    if (lane == 0) red[wid] = m;
+    __syncthreads();
+    if (tid == 0) {
+        m = max(max(red[0], red[1]), max(red[2], red[3]));
+        int s = 0;
+        if (m) {
+            int e;
+            (void)frexpf(__uint_as_float(m), &e);
+            s = mf_f16_shift(e);
+        }
+        s_shift = s;
+        scale[row] = ldexpf(1.f, s);
+        inv_scale[row] = ldexpf(1.f, -s);
+    }
+    __syncthreads();
+    const float sc = ldexpf(1.f, s_shift);
+    unsigned cnt = 0u, nz = 0u;
+    for (int64_t c = tid; c < ld / 8; c += 256) {
+        const float4 v0 = reinterpret_cast<const float4*>(a)[2 * c], v1 = reinterpret_cast<const float4*>(a)[2 * c + 1];
+        const float xs[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
+        unsigned h[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const float x = xs[k];
+            unsigned b = 0u;
+            if (8 * c + k < nvoxel) {
+                b = __builtin_bit_cast(uint16_t, (_Float16)(x * sc));
+                if (x != x) b = 0x7e00u;
+                else if (fabsf(x) <= 3.0e38f && x != 0.f) {
+                    ++nz;
+                    if ((b & 0x7fffu) < 0x0400u) ++cnt;
+                }
+            }
+            h[k] = b;
+        }
+        sart_u4v o;
+        o.x = h[0] | (h[1] << 16);
+        o.y = h[2] | (h[3] << 16);
+        o.z = h[4] | (h[5] << 16);
+        o.w = h[6] | (h[7] << 16);
+        reinterpret_cast<sart_u4v*>(dst + row * ld)[c] = o;
+    }
+    if (counts != nullptr) {  // (uniform for the grid)
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            cnt += (unsigned)__shfl_xor((int)cnt, o, kWave);
+            nz += (unsigned)__shfl_xor((int)nz, o, kWave);
+        }
+        __syncthreads();  // red[] was read by thread 0 above
+        if (lane == 0) red[wid] = cnt, red2[wid] = nz;
+        __syncthreads();
+        if (tid == 0) {
+            const unsigned long long t = (unsigned long long)red[0] + red[1] + red[2] + red[3];
+            const unsigned long long u = (unsigned long long)red2[0] + red2[1] + red2[2] + red2[3];
+            if (t) atomicAdd(counts, t);
+            if (u) atomicAdd(counts + 1, u);
+        }
+    }
+}
+
+// v[i] *= rinv[i]: the per-row operands of the frame setup's back-projections (max(ghat, 0) of the initial guess,
+// a ghat of the log solver's observed back-projection) on a row-scaled f16 shard
+__global__ __launch_bounds__(256) void k_scale_rows(float* __restrict__ v, const float* __restrict__ rinv, int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) v[i] *= rinv[i];
 }
 
 // out[c] = scale[c] * sum_s partial[s][c]   (fixed summation order -> deterministic)
@@ -307,11 +428,11 @@ static constexpr int64_t cols_per_vec() {
 template <int EPI, typename AT>
 static void launch_forward_epi(const AT* A, int64_t ld, int64_t nrows, int64_t nrows_pad, const float* x,
                                const float* ghat, const float* arow, float* out_f, float* out_w, double* Fpart,
-                               const SartState* st, hipStream_t stream) {
+                               const SartState* st, hipStream_t stream, const float* rinv) {
     constexpr int RPB = 8;
     const int64_t nblk = (nrows_pad + RPB - 1) / RPB;
     hipLaunchKernelGGL((k_forward<RPB, EPI, AT>), dim3((unsigned)nblk), dim3(256), 0, stream, A, ld, nrows, x, ghat,
-                       arow, out_f, out_w, Fpart, st);
+                       arow, out_f, out_w, Fpart, st, rinv);
 }
 
 int64_t forward_num_blocks(int64_t nrows_pad) { return (nrows_pad + 7) / 8; }
@@ -319,18 +440,22 @@ int64_t forward_num_blocks(int64_t nrows_pad) { return (nrows_pad + 7) / 8; }
 template <typename AT>
 static void launch_forward_t(int epi, const AT* A, int64_t ld, int64_t nrows, int64_t nrows_pad, const float* x,
                              const float* ghat, const float* arow, float* out_f, float* out_w, double* Fpart,
-                             const SartState* st, hipStream_t stream) {
+                             const SartState* st, hipStream_t stream, const float* rinv = nullptr) {
+    if (RtmVec<AT>::kRowScaled && !rinv) throw std::runtime_error("forward: an f16 shard needs its row scales");
     if (nrows_pad % 8 != 0) throw std::runtime_error("forward: padded row count must be a multiple of 8");
     if (ld % 64 != 0) throw std::runtime_error("forward: ld must be a multiple of 64");
     switch (epi) {
         case kEpiPlain:
-            launch_forward_epi<kEpiPlain>(A, ld, nrows, nrows_pad, x, ghat, arow, out_f, out_w, Fpart, st, stream);
+            launch_forward_epi<kEpiPlain>(A, ld, nrows, nrows_pad, x, ghat, arow, out_f, out_w, Fpart, st, stream,
+                                          rinv);
             break;
         case kEpiLinear:
-            launch_forward_epi<kEpiLinear>(A, ld, nrows, nrows_pad, x, ghat, arow, out_f, out_w, Fpart, st, stream);
+            launch_forward_epi<kEpiLinear>(A, ld, nrows, nrows_pad, x, ghat, arow, out_f, out_w, Fpart, st, stream,
+                                          rinv);
             break;
         case kEpiLog:
-            launch_forward_epi<kEpiLog>(A, ld, nrows, nrows_pad, x, ghat, arow, out_f, out_w, Fpart, st, stream);
+            launch_forward_epi<kEpiLog>(A, ld, nrows, nrows_pad, x, ghat, arow, out_f, out_w, Fpart, st, stream,
+                                          rinv);
             break;
         default:
             throw std::runtime_error("forward: unknown epilogue");
@@ -350,11 +475,19 @@ void launch_forward(int epi, const bf16_t* A, int64_t ld, int64_t nrows, int64_t
     launch_forward_t(epi, A, ld, nrows, nrows_pad, x, ghat, arow, out_f, out_w, Fpart, st, stream);
 }
 
+void launch_forward(int epi, const f16s_t* A, int64_t ld, int64_t nrows, int64_t nrows_pad, const float* x,
+                    const float* ghat, const float* arow, float* out_f, float* out_w, double* Fpart,
+                    const SartState* st, hipStream_t stream, const float* rinv) {
+    launch_forward_t(epi, A, ld, nrows, nrows_pad, x, ghat, arow, out_f, out_w, Fpart, st, stream, rinv);
+}
+
 template <typename AT>
-static void launch_rowsum_t(const AT* A, int64_t ld, int64_t nrows, double* out, hipStream_t stream) {
+static void launch_rowsum_t(const AT* A, int64_t ld, int64_t nrows, double* out, hipStream_t stream,
+                            const float* rinv = nullptr) {
     if (nrows <= 0) return;
+    if (RtmVec<AT>::kRowScaled && !rinv) throw std::runtime_error("rowsum: an f16 shard needs its row scales");
     if (ld % 64 != 0) throw std::runtime_error("rowsum: ld must be a multiple of 64");
-    hipLaunchKernelGGL((k_rowsum_f64<AT>), dim3((unsigned)nrows), dim3(256), 0, stream, A, ld, nrows, out);
+    hipLaunchKernelGGL((k_rowsum_f64<AT>), dim3((unsigned)nrows), dim3(256), 0, stream, A, ld, nrows, out, rinv);
     check_launch("k_rowsum_f64");
 }
 
@@ -364,6 +497,11 @@ void launch_rowsum_f64(const float* A, int64_t ld, int64_t nrows, double* out, h
 
 void launch_rowsum_f64(const bf16_t* A, int64_t ld, int64_t nrows, double* out, hipStream_t stream) {
     launch_rowsum_t(A, ld, nrows, out, stream);
+}
+
+void launch_rowsum_f64(const f16s_t* A, int64_t ld, int64_t nrows, double* out, hipStream_t stream,
+                       const float* rinv) {
+    launch_rowsum_t(A, ld, nrows, out, stream, rinv);
 }
 
 // Choose the number of row splits so that the grid has >= ~2048 workgroups (8 per CU on 256 CUs)
@@ -401,14 +539,21 @@ void launch_backproject(const bf16_t* A, int64_t ld, int64_t nrows, const float*
     launch_backproject_t(A, ld, nrows, w, nsplit, partial, st, stream);
 }
 
+// w already carries the rows' 1 / s_p (the forward's epilogue, launch_scale_rows)
+void launch_backproject(const f16s_t* A, int64_t ld, int64_t nrows, const float* w, int nsplit, float* partial,
+                        const SartState* st, hipStream_t stream) {
+    launch_backproject_t(A, ld, nrows, w, nsplit, partial, st, stream);
+}
+
 template <typename AT>
 static void launch_colsum_t(const AT* A, int64_t ld, int64_t nrows, int nsplit, double* partial,
-                            hipStream_t stream) {
+                            hipStream_t stream, const float* rinv = nullptr) {
+    if (RtmVec<AT>::kRowScaled && !rinv) throw std::runtime_error("colsum: an f16 shard needs its row scales");
     if (ld % 64 != 0) throw std::runtime_error("colsum: ld must be a multiple of 64");
     const int64_t ncb = (ld / cols_per_vec<AT>() + 255) / 256;
     const int64_t rps = (nrows + nsplit - 1) / nsplit;
     hipLaunchKernelGGL((k_colsum_f64<AT>), dim3((unsigned)ncb, (unsigned)nsplit), dim3(256), 0, stream, A, ld, nrows,
-                       rps, partial);
+                       rps, partial, rinv);
     check_launch("k_colsum_f64");
 }
 
@@ -418,6 +563,28 @@ void launch_colsum_f64(const float* A, int64_t ld, int64_t nrows, int nsplit, do
 
 void launch_colsum_f64(const bf16_t* A, int64_t ld, int64_t nrows, int nsplit, double* partial, hipStream_t stream) {
     launch_colsum_t(A, ld, nrows, nsplit, partial, stream);
+}
+
+void launch_colsum_f64(const f16s_t* A, int64_t ld, int64_t nrows, int nsplit, double* partial, hipStream_t stream,
+                       const float* rinv) {
+    launch_colsum_t(A, ld, nrows, nsplit, partial, stream, rinv);
+}
+
+void launch_f32_to_f16_rows(const float* src, int64_t n, int64_t ld, int64_t nvoxel, f16s_t* dst, float* scale,
+                            float* inv_scale, unsigned long long* counts, hipStream_t stream) {
+    if (n <= 0) return;
+    if (ld % 8 != 0 || nvoxel < 0 || nvoxel > ld)
+        throw std::runtime_error("f32_to_f16_rows: ld must be a multiple of 8 and hold nvoxel columns");
+    if (!scale || !inv_scale) throw std::runtime_error("f32_to_f16_rows: scale arrays required");
+    hipLaunchKernelGGL(k_f32_to_f16_rows, dim3((unsigned)n), dim3(256), 0, stream, src, ld, nvoxel, dst, scale,
+                       inv_scale, counts);
+    check_launch("k_f32_to_f16_rows");
+}
+
+void launch_scale_rows(float* v, const float* rinv, int64_t n, hipStream_t stream) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(k_scale_rows, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, v, rinv, n);
+    check_launch("k_scale_rows");
 }
 
 void launch_f32_to_bf16(const float* src, int64_t n, bf16_t* dst, hipStream_t stream) {

@@ -179,8 +179,27 @@ typedef unsigned sart_u4v __attribute__((ext_vector_type(4)));
 template <typename AT>
 struct RtmVec;
 
+// Row-scaled f16 storage (opt-in, --rtm_f16): element (p, v) holds the f16 bit pattern of A[p][v] s_p, with a
+// power-of-two scale s_p per row (2^mf_f16_shift(e) for a row maximum m 2^e: scaled maxima in [2^13, 2^14)) kept
+// beside the shard as rsc[p] = s_p, rsc[nrows_pad + p] = 1 / s_p. Eleven significant bits against bf16's eight at
+// the same two bytes; widening to fp32 is exact, and so is every multiplication by 1 / s_p. A tag type of its own:
+// bf16_t is a plain uint16_t and the launchers overload on the element type.
+struct f16s_t {
+    uint16_t bits;
+};
+static_assert(sizeof(f16s_t) == 2, "f16s_t is a bare f16 bit pattern");
+typedef _Float16 sart_h8v __attribute__((ext_vector_type(8)));
+
+// The f16 scale exponent 14 - e of a maximum m 2^e (m in [0.5, 1)), clamped so that the scale and its inverse are
+// both normal floats (a maximum below 2^-106 would otherwise give an infinite scale, and w * inf non-finite pieces)
+__device__ __host__ __forceinline__ int mf_f16_shift(int e) {
+    const int s = 14 - e;
+    return s > 120 ? 120 : (s < -120 ? -120 : s);
+}
+
 template <>
 struct RtmVec<float> {
+    static constexpr bool kRowScaled = false;
     static constexpr int NF4 = 1;  // float4 per 16-byte load
     __device__ __forceinline__ static void load(const float* row, int64_t v, float4 (&o)[1]) {
         o[0] = load_stream(reinterpret_cast<const float4*>(row) + v);
@@ -194,6 +213,7 @@ __device__ __forceinline__ float4 bf16x4_to_f4(unsigned lo, unsigned hi) {
 
 template <>
 struct RtmVec<bf16_t> {
+    static constexpr bool kRowScaled = false;
     static constexpr int NF4 = 2;
     __device__ __forceinline__ static void load(const bf16_t* row, int64_t v, float4 (&o)[2]) {
 #if SART_STREAM_NT
@@ -203,6 +223,24 @@ struct RtmVec<bf16_t> {
 #endif
         o[0] = bf16x4_to_f4(u.x, u.y);
         o[1] = bf16x4_to_f4(u.z, u.w);
+    }
+};
+
+// 8 f16 columns per 16-byte load, widened exactly (v_cvt_f32_f16); the row's 1 / s_p is applied by the kernels'
+// epilogues (forward, row sums) or carried by the per-row operand (back-projection, column sums)
+template <>
+struct RtmVec<f16s_t> {
+    static constexpr bool kRowScaled = true;
+    static constexpr int NF4 = 2;
+    __device__ __forceinline__ static void load(const f16s_t* row, int64_t v, float4 (&o)[2]) {
+#if SART_STREAM_NT
+        const sart_u4v u = __builtin_nontemporal_load(reinterpret_cast<const sart_u4v*>(row) + v);
+#else
+        const sart_u4v u = reinterpret_cast<const sart_u4v*>(row)[v];
+#endif
+        const sart_h8v h = __builtin_bit_cast(sart_h8v, u);
+        o[0] = make_float4((float)h[0], (float)h[1], (float)h[2], (float)h[3]);
+        o[1] = make_float4((float)h[4], (float)h[5], (float)h[6], (float)h[7]);
     }
 };
 

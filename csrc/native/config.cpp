@@ -87,6 +87,10 @@ std::string usage() {
            "                              block; all-reduce of A x per iteration) instead of by pixel rows.\n"
            "  --rtm_bf16                  Store the RTM in bf16 on the GPU (half the memory and bytes per sweep;\n"
            "                              products and sums stay fp32).\n"
+           "  --rtm_f16                   Store the RTM on the GPU as f16 with a power-of-two scale per pixel row\n"
+           "                              (the same two bytes as --rtm_bf16 with 11 significant bits instead of\n"
+           "                              8; two-pass kernels, and the matrix cores with --batch_frames).\n"
+           "                              Exclusive with --rtm_bf16.\n"
            "  --rtm_format F              auto | dense | sparse: keep a sparse RTM sparse (CSR + CSC; the GPU\n"
            "                              solvers and the CPU solver, pixel-row shards). auto: when every RTM dataset is\n"
            "                              sparse COO with at most 10 % non-zeros. [default: auto]\n"
@@ -118,6 +122,7 @@ Config parse_arguments(const std::vector<std::string>& argv) {
         {"--logarithmic", &c.logarithmic}, {"--no_guess", &c.no_guess},   {"--use_cpu", &c.use_cpu},
         {"--parallel_read", &c.parallel_read}, {"--resume", &c.resume}, {"--two_pass", &c.two_pass},
         {"--partition_voxels", &c.partition_voxels}, {"--rtm_bf16", &c.rtm_bf16},
+        {"--rtm_f16", &c.rtm_f16},
     };
     const std::map<std::string, std::string> alias = {
         {"-o", "--output_file"},           {"-t", "--time_range"},          {"-w", "--wavelength_threshold"},
@@ -178,9 +183,13 @@ Config parse_arguments(const std::vector<std::string>& argv) {
         throw Error("Argument partition_voxels applies to the single-frame GPU solver only.");
     if (c.rtm_bf16 && (c.use_cpu || c.partition_voxels))
         throw Error("Argument rtm_bf16 applies to the GPU solvers with pixel-row shards only.");
+    if (c.rtm_f16 && c.rtm_bf16)
+        throw Error("Arguments rtm_f16 and rtm_bf16 are exclusive: one storage format per RTM.");
+    if (c.rtm_f16 && (c.use_cpu || c.partition_voxels))
+        throw Error("Argument rtm_f16 applies to the GPU solvers with pixel-row shards only.");
     if (c.rtm_format != "auto" && c.rtm_format != "dense" && c.rtm_format != "sparse")
         throw Error("Argument rtm_format must be auto, dense or sparse, " + c.rtm_format + " given.");
-    if (c.rtm_format == "sparse" && (c.partition_voxels || c.rtm_bf16 || (c.use_cpu && c.batch_frames > 1)))
+    if (c.rtm_format == "sparse" && (c.partition_voxels || c.rtm_bf16 || c.rtm_f16 || (c.use_cpu && c.batch_frames > 1)))
         throw Error("Argument rtm_format sparse applies to fp32 pixel-row shards (and not to CPU batches).");
     if (c.input_files.size() < 2)
         throw Error("At least two input file, one with RTM and one with image, are required, " +

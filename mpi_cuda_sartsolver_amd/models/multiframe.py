@@ -69,6 +69,9 @@ class MultiFrameSARTSolver:
         cfg.check_interval = max(1, int(check_interval))
         cfg.mf_frames = self.batch
         cfg.rtm_bf16 = bool(getattr(rtm, "is_bf16", False))  # bf16 storage: bf16 MFMA projections
+        if getattr(rtm, "is_f16", False):  # row-scaled f16 storage: the same kernels on the f16 MFMA ("f16-storage")
+            cfg.rtm_f16 = True
+            cfg.row_scale = rtm.row_scale.data_ptr()
         # fp32 storage: fp32 MFMA, or A split into hi + lo bf16 on the bf16 matrix cores (None: the engine's
         # default, on for batches of 32 / 64 frames, env SART_MF_X3)
         cfg.mf_split_a = -1 if split_a is None else int(bool(split_a))
@@ -87,7 +90,7 @@ class MultiFrameSARTSolver:
         self.split_a = bool(self.engine.split_a)
         # operand pieces of the projections: "f16x2" (split-A default: range-safe f16 pairs, per-row scales in the
         # forward, per-column in the back-projection), "bf16x2" / "bf16x3" (SART_MF_FWD16=0 / SART_MF_BWD16=0),
-        # "fp32" (fp32 MFMA) or "bf16-storage"
+        # "fp32" (fp32 MFMA), "bf16-storage" or "f16-storage"
         self.forward_split = str(self.engine.forward_split)
         self.backproject_split = str(self.engine.backproject_split)
 

@@ -1,7 +1,8 @@
 """fp64 SART oracle on the device (torch), for shards too large for the host oracle.
 
 Same GPU semantics as :func:`models.reference.sart_gpu_semantics` (reference sartsolver_cuda.cpp:138-354,
-sart_kernels.cu), fixed iteration count, evaluated in fp64 over a device-resident fp32 (or bf16) row shard.
+sart_kernels.cu), fixed iteration count, evaluated in fp64 over a device-resident fp32 (or bf16, or row-scaled f16:
+dequantised block by block) row shard.
 The shard is converted to fp64 one row block at a time, so the oracle needs no fp64 copy of the matrix
 (the 275 GB single-GPU shard works). With a communicator the shards of all ranks form one problem: the
 voxel-length sums are all-reduced exactly as the engine does (row shards only).
@@ -44,8 +45,12 @@ def sart_oracle_f64(rtm: DenseRTM, g, iterations: int, *, logarithmic: bool = Fa
     blocks = [(r0, min(P, r0 + rb)) for r0 in range(0, P, rb)]
     f64 = torch.float64
 
+    f16 = bool(getattr(rtm, "is_f16", False))
+    rinv = rtm.row_scale[rtm.nrows_pad:].to(f64) if f16 else None
+
     def Ablk(r0, r1):
-        return A[r0:r1, :V].to(f64)
+        a = A[r0:r1, :V].to(f64)
+        return a * rinv[r0:r1, None] if f16 else a  # H / s_p, exact
 
     g = torch.as_tensor(np.asarray(g, dtype=np.float64), device=dev)
     gf = torch.where(torch.isfinite(g), g, torch.full_like(g, -1.0))

@@ -6,7 +6,8 @@ freed. Here the shard lives only in HBM: it is filled either on the device (synt
 streaming row blocks from HDF5 through a pinned staging buffer (``fill_rows``), so a 275 GB shard
 needs no 275 GB of host RAM.
 
-Layout: row-major fp32 (or bf16), ``nrows_pad x ld`` with zero padding. ``ld`` is chosen so the fused
+Layout: row-major fp32 (or bf16, or row-scaled f16 with one power-of-two scale per row), ``nrows_pad x ld`` with
+zero padding. ``ld`` is chosen so the fused
 sweep can split the columns into slabs (``choose_ld``); otherwise it is a multiple of 64.
 """
 from __future__ import annotations
@@ -36,7 +37,7 @@ def choose_ld(nvoxel: int, max_waste: float = 0.10, storage: str = "fp32") -> in
     """Padded row length (native ``sart::choose_ld``, csrc/engine/geometry.cpp: the single source of truth
     for the engine, both drivers and this package): the variant 6 width with the lowest estimated time per
     row, else a multiple of 8192 (variant 3), else the next multiple of 64. fp32 shards also consider slabs of
-    7 / 6 KiB columns (kw 7 / 6), bf16 shards keep the 8-KiB slabs of their tiles."""
+    7 / 6 KiB columns (kw 7 / 6), bf16 and f16 shards keep the 8-KiB slabs of 16-bit tiles."""
     return int(hip().choose_ld(int(nvoxel), float(max_waste), storage == "fp32"))
 
 
@@ -83,11 +84,23 @@ class DenseRTM:
         self.nrows_pad = round_up(self.npixel, row_align)
         # storage precision: "fp32" (the reference's) or "bf16" (opt-in: half the HBM bytes per sweep and twice
         # the matrix per GPU; the two-pass kernels widen to fp32 in registers, sums stay fp32 / fp64)
-        if storage not in ("fp32", "bf16"):
-            raise ValueError("storage must be 'fp32' or 'bf16'")
+        # "f16" (opt-in): f16 of A s_p with a power-of-two scale s_p per row (utils/f16rows.py: scaled row maxima in
+        # [2^13, 2^14)): 11 significant bits at bf16's two bytes, exact widening; the solvers solve H / s_p.
+        # ``row_scale`` holds [nrows_pad] scales, then [nrows_pad] inverses, and travels with the shard.
+        if storage not in ("fp32", "bf16", "f16"):
+            raise ValueError("storage must be 'fp32', 'bf16' or 'f16'")
+        if storage == "f16" and (self.col_offset != 0 or self.nvoxel != self.nvoxel_total):
+            raise ValueError("row-scaled f16 storage is for row shards")
         self.storage = storage
-        dt = torch.bfloat16 if storage == "bf16" else torch.float32
+        dt = {"fp32": torch.float32, "bf16": torch.bfloat16, "f16": torch.float16}[storage]
         self.A = torch.empty((self.nrows_pad, self.ld), dtype=dt, device=self.device)
+        self.row_scale = None
+        self.flushed = None
+        if storage == "f16":
+            self.row_scale = torch.ones(2 * self.nrows_pad, dtype=torch.float32, device=self.device)
+            # counted by the conversion kernel: [0] non-zero inputs stored as zero or as an f16 subnormal, [1] all
+            # non-zero inputs
+            self.flushed = torch.zeros(2, dtype=torch.int64, device=self.device)
 
     # ------------------------------------------------------------------ construction helpers
     @property
@@ -98,17 +111,49 @@ class DenseRTM:
     def is_bf16(self) -> bool:
         return self.storage == "bf16"
 
-    # rows converted per block when an fp32 source is stored as bf16 (bounds the fp32 scratch to ~256 MiB)
+    @property
+    def is_f16(self) -> bool:
+        return self.storage == "f16"
+
+    @property
+    def is_16bit(self) -> bool:
+        return self.storage != "fp32"
+
+    @property
+    def flushed_count(self) -> int:
+        """Non-zero inputs stored as zero or as an f16 subnormal so far (f16 shards; 0 otherwise)."""
+        return int(self.flushed[0].item()) if self.flushed is not None else 0
+
+    @property
+    def nonzero_count(self) -> int:
+        """Non-zero finite inputs converted so far (f16 shards; 0 otherwise)."""
+        return int(self.flushed[1].item()) if self.flushed is not None else 0
+
+    def dequantised(self) -> torch.Tensor:
+        """The matrix the solvers solve, fp32 [npixel, nvoxel] on the device (f16: H / s_p, exact)."""
+        a = self.A[: self.npixel, : self.nvoxel].float()
+        if self.is_f16:
+            a = a * self.row_scale[self.nrows_pad: self.nrows_pad + self.npixel, None]
+        return a
+
+    # rows converted per block when an fp32 source is stored in 16 bits (bounds the fp32 scratch to ~256 MiB)
     def _block_rows(self) -> int:
         return max(64, min(self.nrows_pad, (256 << 20) // (4 * self.ld)))
 
     def _store_rows(self, local_row: int, src) -> None:
-        """Store a device fp32 block [n, ld] into rows [local_row, local_row + n) (native RNE conversion for bf16)."""
+        """Store a device fp32 block [n, ld] into rows [local_row, local_row + n) (native RNE conversion for bf16;
+        the row-scaling conversion kernel for f16, which also writes the rows' scales)."""
         n = src.shape[0]
-        if not self.is_bf16:
+        if not self.is_16bit:
             self.A[local_row: local_row + n].copy_(src)
             return
         src = src.contiguous()
+        if self.is_f16:
+            hip().f32_to_f16_rows(src.data_ptr(), n, self.ld, self.nvoxel, self.A[local_row].data_ptr(),
+                                  self.row_scale[local_row:].data_ptr(),
+                                  self.row_scale[self.nrows_pad + local_row:].data_ptr(), self.flushed.data_ptr(),
+                                  self.stream_handle)
+            return
         hip().f32_to_bf16(src.data_ptr(), n * self.ld, self.A[local_row].data_ptr(), self.stream_handle)
 
     @property
@@ -133,11 +178,11 @@ class DenseRTM:
         column shards of one global matrix agree bit for bit."""
         m = cls(npixel, nvoxel, row_offset, device=device, ld=ld, col_offset=col_offset, nvoxel_total=nvoxel_total,
                 storage=storage)
-        if not m.is_bf16:
+        if not m.is_16bit:
             hip().synth_matrix(m.A.data_ptr(), m.ld, m.nrows_pad, m.npixel, m.nvoxel, m.row_offset, int(seed),
                                float(lo), float(hi), m.stream_handle, m.col_offset, m.nvoxel_total)
             return m
-        # bf16: generate fp32 row blocks of the same global matrix and round them into the shard
+        # bf16 / f16: generate fp32 row blocks of the same global matrix and round them into the shard
         nb = m._block_rows()
         scratch = torch.empty((nb, m.ld), dtype=torch.float32, device=m.device)
         for r0 in range(0, m.nrows_pad, nb):
@@ -164,7 +209,7 @@ class DenseRTM:
         """Copy a host block of rows [local_row, local_row + len(block)) x [0, nvoxel) into HBM."""
         t = torch.as_tensor(block, dtype=torch.float32)
         n = t.shape[0]
-        if not self.is_bf16:
+        if not self.is_16bit:
             self.A[local_row: local_row + n, : self.nvoxel].copy_(t, non_blocking=t.is_pinned())
             return
         nb = self._block_rows()
@@ -181,7 +226,28 @@ class DenseRTM:
         m = DenseRTM(self.npixel, self.nvoxel, self.row_offset, device=self.device, ld=self.ld,
                      row_align=self.nrows_pad, col_offset=self.col_offset, nvoxel_total=self.nvoxel_total,
                      storage="bf16")
-        src = self.A if not self.is_bf16 else self.A.float()
+        src = self._fp32_padded()
+        nb = m._block_rows()
+        for r0 in range(0, self.nrows_pad, nb):
+            m._store_rows(r0, src[r0: r0 + nb])
+        torch.cuda.synchronize(self.device)
+        return m
+
+    def _fp32_padded(self) -> torch.Tensor:
+        """The stored matrix as fp32 [nrows_pad, ld] (the shard itself when it is fp32)."""
+        if not self.is_16bit:
+            return self.A
+        a = self.A.float()
+        if self.is_f16:
+            a = a * self.row_scale[self.nrows_pad:, None]
+        return a
+
+    def to_f16(self) -> "DenseRTM":
+        """Row-scaled f16 copy of this row shard (same geometry), converted by the native kernel."""
+        m = DenseRTM(self.npixel, self.nvoxel, self.row_offset, device=self.device, ld=self.ld,
+                     row_align=self.nrows_pad, col_offset=self.col_offset, nvoxel_total=self.nvoxel_total,
+                     storage="f16")
+        src = self._fp32_padded()
         nb = m._block_rows()
         for r0 in range(0, self.nrows_pad, nb):
             m._store_rows(r0, src[r0: r0 + nb])
@@ -189,7 +255,7 @@ class DenseRTM:
         return m
 
     def to_host(self):
-        return self.A[: self.npixel, : self.nvoxel].float().cpu().numpy()
+        return self.dequantised().cpu().numpy()
 
 
 class SparseRTM:
