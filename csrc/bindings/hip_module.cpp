@@ -9,6 +9,7 @@
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
 
+#include <cstddef>
 #include <cstdint>
 #include <cstring>
 #include <stdexcept>
@@ -364,6 +365,7 @@ static void bind_engine(py::module_& m) {
             d["lead"] = s.lead;
             d["src_extrap"] = s.src_extrap;
             d["drift"] = s.drift;
+            d["stage_window"] = s.stage_window;
             d["host_wait_ms"] = s.host_wait_ms;
             d["host_stage_ms"] = s.host_stage_ms;
             d["host_src_ms"] = s.host_src_ms;
@@ -372,9 +374,220 @@ static void bind_engine(py::module_& m) {
         });
 }
 
+// Struct layouts for the tests (tests/mf_refill_model.py decodes raw device bytes of MfState / MfQueue with these, so
+// python keeps no second copy of the structs): {"nbytes", "fields": {name: (offset, numpy dtype string, count)}}
+#define MF_FIELD(S, name, dtype) \
+    fields[#name] = py::make_tuple((int)offsetof(S, name), dtype, (int)(sizeof(S::name) / mf_dtype_size(dtype)))
+
+static size_t mf_dtype_size(const char* dtype) { return (size_t)(dtype[2] - '0'); }
+
+static py::dict mf_state_layout() {
+    using S = sart::MfState;
+    py::dict fields;
+    MF_FIELD(S, G, "<f8");
+    MF_FIELD(S, conv_prev, "<f8");
+    MF_FIELD(S, conv, "<f8");
+    MF_FIELD(S, done, "<i4");
+    MF_FIELD(S, status, "<i4");
+    MF_FIELD(S, iters, "<i4");
+    MF_FIELD(S, sweep, "<i4");
+    MF_FIELD(S, max_iter, "<i4");
+    MF_FIELD(S, all_done, "<i4");
+    MF_FIELD(S, nf, "<i4");
+    MF_FIELD(S, flags, "<u8");
+    MF_FIELD(S, tol, "<f8");
+    MF_FIELD(S, rollback, "<u8");
+    MF_FIELD(S, sweep0, "<i4");
+    py::dict d;
+    d["nbytes"] = (int)sizeof(S);
+    d["fields"] = fields;
+    return d;
+}
+
+static py::dict mf_finish_layout() {
+    using S = sart::MfFinish;
+    py::dict fields;
+    MF_FIELD(S, frame, "<i4");
+    MF_FIELD(S, status, "<i4");
+    MF_FIELD(S, iters, "<i4");
+    MF_FIELD(S, flags, "<i4");
+    MF_FIELD(S, warm_from, "<i4");
+    MF_FIELD(S, warm_iter, "<i4");
+    MF_FIELD(S, warm_live, "<i4");
+    MF_FIELD(S, conv, "<f8");
+    MF_FIELD(S, norm, "<f8");
+    py::dict d;
+    d["nbytes"] = (int)sizeof(S);
+    d["fields"] = fields;
+    return d;
+}
+
+static py::dict mf_queue_layout() {
+    using S = sart::MfQueue;
+    py::dict fields;
+    MF_FIELD(S, q_head, "<i8");
+    MF_FIELD(S, q_tail, "<i8");
+    MF_FIELD(S, fin, "<i8");
+    MF_FIELD(S, drained, "<i8");
+    MF_FIELD(S, qcap, "<i4");
+    MF_FIELD(S, rcap, "<i4");
+    MF_FIELD(S, chain, "<i4");
+    MF_FIELD(S, admit_cap, "<i4");
+    MF_FIELD(S, src_age, "<i4");
+    MF_FIELD(S, src_finished, "<i4");
+    MF_FIELD(S, lead, "<i4");
+    MF_FIELD(S, src_extrap, "<f4");
+    MF_FIELD(S, src_live, "<i4");
+    MF_FIELD(S, x0_below, "<i8");
+    MF_FIELD(S, n_ret, "<i4");
+    MF_FIELD(S, n_adm, "<i4");
+    MF_FIELD(S, upd_any, "<i4");
+    MF_FIELD(S, skip_bwd, "<i4");
+    MF_FIELD(S, xlast_frame, "<i4");
+    MF_FIELD(S, xlast_iter, "<i4");
+    MF_FIELD(S, xlast_slot, "<i4");
+    MF_FIELD(S, xlast_norm, "<f8");
+    MF_FIELD(S, xlast2_frame, "<i4");
+    MF_FIELD(S, drift_frame1, "<i4");
+    MF_FIELD(S, drift_frame2, "<i4");
+    MF_FIELD(S, xlast2_norm, "<f8");
+    MF_FIELD(S, drift_norm1, "<f8");
+    MF_FIELD(S, drift_norm2, "<f8");
+    MF_FIELD(S, drift, "<f4");
+    MF_FIELD(S, src_kind, "<i4");
+    MF_FIELD(S, src_slot, "<i4");
+    MF_FIELD(S, src_frame, "<i4");
+    MF_FIELD(S, src_iter, "<i4");
+    MF_FIELD(S, src_norm, "<f8");
+    MF_FIELD(S, slot_frame, "<i4");
+    MF_FIELD(S, slot_warm_from, "<i4");
+    MF_FIELD(S, slot_warm_iter, "<i4");
+    MF_FIELD(S, slot_warm_live, "<i4");
+    MF_FIELD(S, slot_norm, "<f8");
+    MF_FIELD(S, ret_pos, "<i4");
+    MF_FIELD(S, ret_prev, "<i4");
+    MF_FIELD(S, adm_pos, "<i4");
+    MF_FIELD(S, adm_kind, "<i4");
+    MF_FIELD(S, q_frame, "<i4");
+    MF_FIELD(S, q_cold, "<i4");
+    MF_FIELD(S, q_norm, "<f8");
+    MF_FIELD(S, q_G, "<f8");
+    py::dict log = mf_finish_layout();  // MfFinish log[kMfQueueMax]: a sub-layout at its offset
+    log["offset"] = (int)offsetof(S, log);
+    log["count"] = (int)(sizeof(S::log) / sizeof(sart::MfFinish));
+    py::dict d;
+    d["nbytes"] = (int)sizeof(S);
+    d["fields"] = fields;
+    d["log"] = log;
+    py::dict src;  // MfSrc
+    src["none"] = (int)sart::kSrcNone, src["slot"] = (int)sart::kSrcSlot, src["last"] = (int)sart::kSrcLast;
+    src["host_x0"] = (int)sart::kSrcHostX0, src["cold"] = (int)sart::kSrcCold;
+    d["src"] = src;
+    return d;
+}
+#undef MF_FIELD
+
+// Test entry points of the multi-frame glue kernels (multiframe_glue.hip): thin wrappers over the launchers the
+// engine calls, device pointers as integers (0: null)
+static void bind_mf_glue(py::module_& m) {
+    m.def("mf_state_layout", &mf_state_layout);
+    m.def("mf_queue_layout", &mf_queue_layout);
+    m.def("mf_max_frames", []() { return (int)sart::kMfMaxFrames; });
+    m.def("mf_queue_max", []() { return (int)sart::kMfQueueMax; });
+    m.def("mf_weights_num_blocks", &sart::mf_weights_num_blocks);
+    m.def("lds_fill", [](unsigned word, uintptr_t sink, uintptr_t stream) {
+        sart::launch_lds_fill(word, P<unsigned>(sink), S(stream));
+    });
+    m.def("mf_state_begin", [](uintptr_t st, uintptr_t G, int nused, double tol, int max_iter, int nf,
+                               uintptr_t stream) {
+        sart::launch_mf_state_begin(P<sart::MfState>(st), P<const double>(G), nused, tol, max_iter, nf, S(stream));
+    }, py::arg("st"), py::arg("G"), py::arg("nused"), py::arg("tol"), py::arg("max_iter"), py::arg("nf"),
+       py::arg("stream"));
+    m.def("mf_queue_begin", [](uintptr_t q, int qcap, int rcap, bool chain, int admit_cap, int src_age,
+                               int64_t x0_below, bool src_finished, bool lead, float src_extrap, float drift,
+                               uintptr_t stream) {
+        sart::launch_mf_queue_begin(P<sart::MfQueue>(q), qcap, rcap, chain, admit_cap, src_age, x0_below, src_finished,
+                                    lead, src_extrap, S(stream), drift);
+    }, py::arg("q"), py::arg("qcap"), py::arg("rcap"), py::arg("chain"), py::arg("admit_cap"), py::arg("src_age"),
+       py::arg("x0_below"), py::arg("src_finished"), py::arg("lead"), py::arg("src_extrap"), py::arg("drift"),
+       py::arg("stream"));
+    m.def("mf_decide", [](uintptr_t st, uintptr_t F2, uintptr_t q, uintptr_t stream) {
+        sart::launch_mf_decide(P<sart::MfState>(st), P<const float>(F2), S(stream), P<sart::MfQueue>(q));
+    }, py::arg("st"), py::arg("F2"), py::arg("q"), py::arg("stream"));
+    m.def("mf_update", [](uintptr_t X, uintptr_t D, uintptr_t O, uintptr_t pen, float alpha, bool logmode,
+                          int64_t nvox, int64_t ld, uintptr_t st, int nf, uintptr_t Xprev, uintptr_t q,
+                          uintptr_t ring, uintptr_t xlast, uintptr_t xlast2, uintptr_t x0, uintptr_t x0q, uintptr_t oq,
+                          uintptr_t starts, uintptr_t stream) {
+        sart::MfRefill rf{};
+        rf.ring = P<float>(ring);
+        rf.xlast = P<float>(xlast);
+        rf.xlast2 = P<float>(xlast2);
+        rf.x0 = P<const double>(x0);
+        rf.x0q = P<const float>(x0q);
+        rf.oq = P<const float>(oq);
+        rf.starts = P<float>(starts);
+        sart::launch_mf_update(P<float>(X), P<const float>(D), P<float>(O), P<const float>(pen), alpha, logmode, nvox,
+                               ld, P<const sart::MfState>(st), nf, S(stream), P<float>(Xprev),
+                               P<const sart::MfQueue>(q), q ? &rf : nullptr);
+    }, py::arg("X"), py::arg("D"), py::arg("O"), py::arg("pen"), py::arg("alpha"), py::arg("logmode"),
+       py::arg("nvox"), py::arg("ld"), py::arg("st"), py::arg("nf"), py::arg("Xprev"), py::arg("q"),
+       py::arg("ring") = 0, py::arg("xlast") = 0, py::arg("xlast2") = 0, py::arg("x0") = 0, py::arg("x0q") = 0,
+       py::arg("oq") = 0, py::arg("starts") = 0, py::arg("stream") = 0);
+    m.def("mf_admit_rows", [](uintptr_t q, uintptr_t ghq, int64_t nrows, int64_t nrows_pad, uintptr_t ray_length,
+                              float len_thres, uintptr_t ghat, uintptr_t arow, int nf, uintptr_t stream) {
+        sart::launch_mf_admit_rows(P<const sart::MfQueue>(q), P<const float>(ghq), nrows, nrows_pad,
+                                   P<const float>(ray_length), len_thres, P<float>(ghat), P<float>(arow), nf,
+                                   S(stream));
+    });
+    m.def("mf_publish", [](uintptr_t q, int64_t q_tail, uintptr_t stream) {
+        sart::launch_mf_publish(P<sart::MfQueue>(q), q_tail, S(stream));
+    });
+    m.def("mf_drained", [](uintptr_t q, int64_t drained, uintptr_t stream) {
+        sart::launch_mf_drained(P<sart::MfQueue>(q), drained, S(stream));
+    });
+    m.def("mf_stage_stats", [](uintptr_t g64q, int64_t e0, int qcap, int k, int64_t nrows, int64_t nrows_pad,
+                               uintptr_t stats, int nf, uintptr_t stream) {
+        sart::launch_mf_stage_stats(P<const double>(g64q), e0, qcap, k, nrows, nrows_pad, P<double>(stats), nf,
+                                    S(stream));
+    });
+    m.def("mf_stage_norm", [](uintptr_t q, uintptr_t g64q, uintptr_t ghq, uintptr_t stats, int64_t e0, int64_t frame0,
+                              bool cold, int k, int64_t nrows, int64_t nrows_pad, int nf, uintptr_t stream) {
+        sart::launch_mf_stage_norm(P<sart::MfQueue>(q), P<const double>(g64q), P<float>(ghq), P<const double>(stats),
+                                   e0, frame0, cold, k, nrows, nrows_pad, nf, S(stream));
+    });
+    m.def("mf_stage_ops", [](uintptr_t ghq, int64_t e0, int qcap, int k, int64_t nrows, int64_t nrows_pad,
+                             uintptr_t ray_length, float len_thres, uintptr_t gpos, uintptr_t wo, int nf,
+                             uintptr_t stream) {
+        sart::launch_mf_stage_ops(P<const float>(ghq), e0, qcap, k, nrows, nrows_pad, P<const float>(ray_length),
+                                  len_thres, P<float>(gpos), P<float>(wo), nf, S(stream));
+    });
+    m.def("mf_stage_cols", [](uintptr_t D, uintptr_t dinv, int64_t e0, int qcap, int k, int64_t nvox, int64_t ld,
+                              int nf, uintptr_t out, uintptr_t stream) {
+        sart::launch_mf_stage_cols(P<const float>(D), P<const float>(dinv), e0, qcap, k, nvox, ld, nf, P<float>(out),
+                                   S(stream));
+    });
+    m.def("mf_weights", [](uintptr_t Fs, int nsplit, int64_t nrows_pad, uintptr_t ghat, uintptr_t arow, bool logmode,
+                           uintptr_t W, uintptr_t F2part, int nf, uintptr_t stream, uintptr_t wmax, int wplane) {
+        sart::launch_mf_weights(P<const float>(Fs), nsplit, nrows_pad, P<const float>(ghat), P<const float>(arow),
+                                logmode, P<float>(W), P<double>(F2part), nf, S(stream), P<unsigned>(wmax), wplane);
+    }, py::arg("Fs"), py::arg("nsplit"), py::arg("nrows_pad"), py::arg("ghat"), py::arg("arow"), py::arg("logmode"),
+       py::arg("W"), py::arg("F2part"), py::arg("nf"), py::arg("stream"), py::arg("wmax") = 0, py::arg("wplane") = 0);
+    m.def("mf_collect", [](uintptr_t part, int nsplit, int64_t ld, int64_t v0, int64_t v1, uintptr_t scale,
+                           uintptr_t D, uintptr_t F2part, int nF2, uintptr_t F2out, int nf, uintptr_t stream) {
+        sart::launch_mf_collect(P<const float>(part), nsplit, ld, v0, v1, P<const float>(scale), P<float>(D),
+                                P<const double>(F2part), nF2, P<float>(F2out), nf, S(stream));
+    });
+    m.def("mf_penalty", [](uintptr_t row_ptr, uintptr_t col, uintptr_t val, int64_t n, float beta, bool logx,
+                           uintptr_t X, int64_t ld, uintptr_t pen, uintptr_t st, int nf, uintptr_t stream) {
+        sart::launch_mf_penalty(P<const int64_t>(row_ptr), P<const int32_t>(col), P<const float>(val), n, beta, logx,
+                                P<const float>(X), ld, P<float>(pen), P<const sart::MfState>(st), nf, S(stream));
+    });
+}
+
 PYBIND11_MODULE(_sart_hip, m) {
     m.doc() = "Hand-written gfx950 (CDNA4) HIP kernels of the SART solver and the native engine";
     bind_engine(m);
+    bind_mf_glue(m);
 
     m.def("arch", []() { return std::string("gfx950"); });
     m.def("state_nbytes", []() { return (int)sizeof(sart::SartState); });

@@ -126,6 +126,10 @@ MultiFrameEngine::MultiFrameEngine(int device, const void* A, int64_t nrows, int
     // in flight and an admitted frame sits several frames of drift away from its source; the start adds that many
     // times the per-frame change between the two newest finished solutions (MfQueue::drift; SART_MF_DRIFT)
     if (const char* e = std::getenv("SART_MF_DRIFT"); e && *e) drift_ = std::atof(e);
+    // staging window (SART_MF_STAGE_WINDOW=w > 0; tests): entry e is staged only once e < fin + w, fin the frames
+    // finished in the latest snapshot, so the queue starves on purpose: w = 1 admits frame f when every earlier frame
+    // has finished (the sequential warm-start chain, through idle plans and xlast), whatever the host's timing
+    if (const char* e = std::getenv("SART_MF_STAGE_WINDOW"); e && *e) stage_window_ = std::max(0, std::atoi(e));
     hip_ok(hipHostMalloc(reinterpret_cast<void**>(&hg64_), (size_t)qcap_ * Pp_ * sizeof(double)), "hipHostMalloc");
     std::memset(hg64_, 0, (size_t)qcap_ * Pp_ * sizeof(double));  // padding rows stay zero
     g64q_.resize((size_t)qcap_ * Pp_);
@@ -636,11 +640,14 @@ bool MultiFrameEngine::series_once(int64_t first, int64_t nframes, const FrameSo
     stats_.src_finished = src_finished_;
     stats_.src_extrap = src_extrap_;
     stats_.drift = chain ? drift_ : 0.0;
+    stats_.stage_window = stage_window_;
     stats_.lead = chain && !x0 && lead_;
 
     int64_t staged = 0;
+    int64_t window_fin = 0;  // frames finished in the latest snapshot (the staging window's base)
     // stage while the queue has room for a unit (nf with a back-projection), up to `limit` frames
     auto stage_upto = [&](int64_t head, int64_t limit) {
+        if (stage_window_ > 0) limit = std::min(limit, window_fin + stage_window_);
         while (staged < std::min(n, limit)) {
             // the first nf frames start from x0 (or cold without it); later ones cold (!chain) or chained
             const bool cold = chain ? (!x0 && staged < NF) : (!x0 || staged >= NF);
@@ -649,7 +656,7 @@ bool MultiFrameEngine::series_once(int64_t first, int64_t nframes, const FrameSo
             const int64_t unit = (cold || cfg_.logarithmic) ? std::min<int64_t>(lim, n - staged)
                                                             : std::max<int64_t>(1, std::min<int64_t>(NF / 4, n - staged));
             if (room < unit) return;
-            const int k = (int)std::min<int64_t>({room, lim, n - staged});
+            const int k = (int)std::min<int64_t>({room, lim, std::min(n, limit) - staged});
             const auto ts = std::chrono::steady_clock::now();
             stage(first, staged, k, src, cold);
             stats_.host_stage_ms += ms_since(ts);
@@ -809,6 +816,7 @@ bool MultiFrameEngine::series_once(int64_t first, int64_t nframes, const FrameSo
             dq.push_back(std::move(b));
             dcv.notify_all();
         }
+        window_fin = fin;
         stage_upto(head, n);
         if (fin < n) issue();  // frames left to finish on the device (a chunk still in flight may finish them)
     }

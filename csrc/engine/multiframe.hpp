@@ -67,6 +67,7 @@ class MultiFrameEngine {
         bool src_finished = false, lead = false;
         double src_extrap = 0.0;
         double drift = 0.0;
+        int stage_window = 0;  // SART_MF_STAGE_WINDOW (0: off)
     };
     const SeriesStats& series_stats() const { return stats_; }
     int64_t nrows() const { return P_; }
@@ -169,6 +170,7 @@ class MultiFrameEngine {
     int graph_chunk_ = 0;
     bool use_graph_ = true, graph_failed_ = false, warm_chunk_ = false;
     double src_extrap_ = 0.0;
+    int stage_window_ = 0;  // entry e is staged only while e < finished frames + window (0: no limit)
     double drift_ = 0.0;  // drift-extrapolated chain starts (MfQueue::drift; SART_MF_DRIFT)
     DeviceArray<MfQueue> q_;
     DeviceArray<float> ghq_, x0q_, oq_, ring_, xlast_, xlast2_, starts_;

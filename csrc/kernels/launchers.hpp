@@ -350,4 +350,6 @@ void launch_mf_queue_begin(MfQueue* q, int qcap, int rcap, bool chain, int admit
                            bool src_finished, bool lead, float src_extrap, hipStream_t stream, float drift = 0.f);
 void launch_mf_state_begin(MfState* st, const double* G, int nused, double tol, int max_iter, int nf,
                            hipStream_t stream);
+// tests: every CU's LDS filled with `word` (sink: one device word, set only if a store was lost)
+void launch_lds_fill(unsigned word, unsigned* sink, hipStream_t stream);
 }  // namespace sart

@@ -476,20 +476,24 @@ __global__ __launch_bounds__(256) void k_mf_update(float* __restrict__ X, const 
         const int kind = q->adm_kind[f];
         const double s_new = q->slot_norm[f];
         const bool chained = kind == kSrcSlot || kind == kSrcLast;
-        const float dgap = (use_drift && chained) ? q->drift * (float)(q->slot_frame[f] - q->src_frame) : 0.f;
+        // (drift_s is written only with use_drift: without it the term must not read that LDS at all -- 0 * whatever
+        // an earlier kernel left there is NaN for a NaN or Inf pattern, and the start value then clamps to 1e-7)
+        const bool drifting = use_drift && chained;
+        const float dgap = drifting ? q->drift * (float)(q->slot_frame[f] - q->src_frame) : 0.f;
         float o[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int64_t vv = v + j;
             float x = 0.f;
             if (vv < nvox) {
+                const float dr = drifting ? dgap * drift_s[vv - v0] : 0.f;
                 if (kind == kSrcSlot) {
                     float xs = X[src_slot * ld + vv];
                     if (cx != 0.f) xs = fmaf(cx, xs - Xprev[src_slot * ld + vv], xs);
-                    x = (float)(((double)xs * src_norm + (double)(dgap * drift_s[vv - v0])) / s_new);
+                    x = (float)(((double)xs * src_norm + (double)dr) / s_new);
                 }
                 else if (kind == kSrcLast)
-                    x = (float)(((double)rf.xlast[vv] * src_norm + (double)(dgap * drift_s[vv - v0])) / s_new);
+                    x = (float)(((double)rf.xlast[vv] * src_norm + (double)dr) / s_new);
                 else if (kind == kSrcHostX0)
                     x = (float)(rf.x0[vv] / s_new);
                 else if (kind == kSrcCold)
@@ -1245,5 +1249,19 @@ void launch_mf_split_w(const float* W, int64_t nrows_pad, int nf, int64_t ldw, b
     check_launch("k_mf_split_w");
 }
 
+// Tests: fills the whole LDS of every CU with one word, so that a later kernel reading LDS it never wrote sees that
+// word (a NaN pattern turns such a read into a wrong result instead of whatever the previous kernel left there)
+constexpr int kLdsWords = 160 * 1024 / 4;
+__global__ __launch_bounds__(256) void k_lds_fill(unsigned word, unsigned* __restrict__ sink) {
+    __shared__ unsigned buf[kLdsWords];
+    for (int i = threadIdx.x; i < kLdsWords; i += 256) buf[i] = word;
+    __syncthreads();
+    if (buf[(threadIdx.x * 97 + blockIdx.x) % kLdsWords] != word) sink[0] = 1u;  // (keeps the stores)
+}
+
+void launch_lds_fill(unsigned word, unsigned* sink, hipStream_t stream) {
+    hipLaunchKernelGGL(k_lds_fill, dim3(2048), dim3(256), 0, stream, word, sink);
+    check_launch("k_lds_fill");
+}
 
 }  // namespace sart

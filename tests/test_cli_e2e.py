@@ -228,3 +228,29 @@ def test_cli_batched_time_series_warm_start(tmp_path, capfd, log):
         walls[mode + "_solve_ms"] = series["series_ms"] if mode == "batched" else sum(r["ms"] for r in recs[1:])
     # the pipelined chain keeps the warm start's iteration savings (round 5: the stale window start tripled them)
     assert walls["batched_iters"] <= 2.0 * walls["sequential_iters"] + 1.0, walls
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("log", [False, True])
+def test_cli_batched_series_window1(tmp_path, capfd, monkeypatch, log):
+    """SART_MF_STAGE_WINDOW=1: frame k is staged only once frames 0 .. k - 1 have finished, so the batched series is
+    the sequential warm-start chain whatever the host's timing (every admission by a plan that runs alone, from the
+    newest finished solution kept on the device): each frame reports its predecessor, finished, as its source, and
+    the output meets the bound the sequential mode meets against the oracle of that chain."""
+    import json
+
+    monkeypatch.setenv("SART_MF_STAGE_WINDOW", "1")
+    case = make_case(str(tmp_path / "c"), cameras=("cam_a", "cam_b", "cam_c"), shapes=((12, 16), (10, 14), (9, 12)),
+                     laplacian=True, nframes=64, saturate=0.02, nvoxel=1024, grid=(16, 8, 8), seed=11)
+    kw = ["-m", "400", "-c", "1e-4", "-l", case.laplacian_file, "-b", "1e-3"] + (["-L"] if log else [])
+    out, prof = str(tmp_path / "window1.h5"), str(tmp_path / "window1.jsonl")
+    assert cli.main(kw + ["--batch_frames", "16", "--profile", prof, "-o", out] + case.files) == 0
+    assert capfd.readouterr().out.count("Processed in:") == 64
+    lines = [json.loads(ln) for ln in open(prof)]
+    recs = {r["frame"]: r for r in lines if "frame" in r}
+    series = [r for r in lines if r.get("series")][0]
+    assert series["stage_window"] == 1 and len(recs) == 64
+    for k in range(1, 64):
+        assert recs[k]["warm_from"] == k - 1 and recs[k].get("warm_live", 0) == 0, recs[k]
+    e, e32 = chain_errors(case, out, log=log, warm=True)
+    assert np.all(e <= CLI_FP32_FACTOR * e32 + 1e-6), (e, e32)

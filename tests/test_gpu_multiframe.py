@@ -40,6 +40,45 @@ def test_multiframe_vs_oracle(log, nframes, batch):
         check_fp32_bound(res[f].solution, A, G[f], L, log=log, iterations=res[f].iterations, beta_laplace=1e-3)
 
 
+def check_chain_provenance(res, starts, stats, A, G, L, x0, log, kw):
+    """Every frame of a chained series: its recorded start value is its named source (warm_from after warm_iter
+    updates: x0, a finished frame's solution rescaled bitwise, or the oracle's iterate of a frame in flight at the
+    oracle's fp32 drift), and the frame matches the oracle started from that value (status, iterations, and every
+    seventh frame's solution at the fp32 bound)."""
+    from mpi_cuda_sartsolver_amd.models.reference import sart_gpu_semantics
+
+    nframes = len(res)
+    norm = G.max(axis=1)
+    for f in range(nframes):
+        wf, wi = res[f].warm_from, res[f].warm_iter
+        if wf < 0:
+            src = x0
+        elif not res[f].warm_live:  # the source had finished: its solution, rescaled (bitwise)
+            assert wi == res[wf].iterations
+            src = res[wf].solution
+        else:  # in flight: the oracle's iterate of the source after wi updates from its own recorded start,
+            # extrapolated along its last update in linear mode (x + c (x - x_prev), MfQueue::src_extrap)
+            def it(n):
+                return sart_gpu_semantics(A, G[wf], L, logarithmic=log, x_prev=starts[wf],
+                                          **dict(kw, max_iterations=n, conv_tolerance=0.0))[0]
+            src = it(wi)
+            c = 0.0 if log else stats["src_extrap"]
+            if c:
+                src = src + c * (src - it(wi - 1))
+            assert wi >= stats["src_age"]
+        want = np.maximum((src / norm[f]).astype(np.float32), np.float32(1e-7))
+        got = (starts[f] / norm[f]).astype(np.float32)
+        if wf < 0 or not res[f].warm_live:
+            np.testing.assert_array_equal(got, want)
+        else:
+            assert np.linalg.norm(got - want) <= 1e-3 * np.linalg.norm(want), f
+        x, st, it = sart_gpu_semantics(A, G[f], L, logarithmic=log, x_prev=starts[f], **kw)
+        assert res[f].status == st and abs(res[f].iterations - it) <= 2, (f, res[f].iterations, it)
+        if f % 7 == 0 or f == nframes - 1:
+            check_fp32_bound(res[f].solution, A, G[f], L, log=log, iterations=res[f].iterations, beta_laplace=1e-3,
+                             x_prev=starts[f])
+
+
 @pytest.mark.parametrize("log", [False, True])
 def test_multiframe_warm_chain(log):
     """Time series with device-side refill: the first frames start from x0, every later frame from the current
@@ -77,35 +116,7 @@ def test_multiframe_warm_chain(log):
     assert first <= cap * (stats["src_age"] + 1) and all(res[f].warm_from >= 0 for f in range(first, nframes))
     assert len({res[f].iterations for f in range(nframes)}) > 1  # slots really refill at different sweeps
     assert any(res[f].warm_live for f in range(nframes))  # sources in flight
-    norm = G.max(axis=1)
-    for f in range(nframes):
-        wf, wi = res[f].warm_from, res[f].warm_iter
-        if wf < 0:
-            src = x0
-        elif not res[f].warm_live:  # the source had finished: its solution, rescaled (bitwise)
-            assert wi == res[wf].iterations
-            src = res[wf].solution
-        else:  # in flight: the oracle's iterate of the source after wi updates from its own recorded start,
-            # extrapolated along its last update in linear mode (x + c (x - x_prev), MfQueue::src_extrap)
-            def it(n):
-                return sart_gpu_semantics(A, G[wf], L, logarithmic=log, x_prev=starts[wf],
-                                          **dict(kw, max_iterations=n, conv_tolerance=0.0))[0]
-            src = it(wi)
-            c = 0.0 if log else stats["src_extrap"]
-            if c:
-                src = src + c * (src - it(wi - 1))
-            assert wi >= stats["src_age"]
-        want = np.maximum((src / norm[f]).astype(np.float32), np.float32(1e-7))
-        got = (starts[f] / norm[f]).astype(np.float32)
-        if wf < 0 or not res[f].warm_live:
-            np.testing.assert_array_equal(got, want)
-        else:
-            assert np.linalg.norm(got - want) <= 1e-3 * np.linalg.norm(want), f
-        x, st, it = sart_gpu_semantics(A, G[f], L, logarithmic=log, x_prev=starts[f], **kw)
-        assert res[f].status == st and abs(res[f].iterations - it) <= 2, (f, res[f].iterations, it)
-        if f % 7 == 0 or f == nframes - 1:
-            check_fp32_bound(res[f].solution, A, G[f], L, log=log, iterations=res[f].iterations, beta_laplace=1e-3,
-                             x_prev=starts[f])
+    check_chain_provenance(res, starts, stats, A, G, L, x0, log, kw)
     # without chain, every frame after the first batch cold-starts even when x0 is given
     cold = s.solve_batch(G[:20], x0=x0)
     assert all(r.warm_from == -1 for r in cold)
@@ -115,6 +126,66 @@ def test_multiframe_warm_chain(log):
     x, st, it = sart_gpu_semantics(A, G[3], L, logarithmic=log, x_prev=x0, **kw)  # the first batch: from x0
     assert cold[3].status == st and abs(cold[3].iterations - it) <= 2
 
+
+@pytest.mark.parametrize("w", [1, 3])
+@pytest.mark.parametrize("log", [False, True])
+def test_multiframe_warm_chain_starved(monkeypatch, log, w):
+    """SART_MF_STAGE_WINDOW=w: entry e is staged only once e < finished + w, so the queue starves whatever the host's
+    timing: slots drain, plans run alone and refill from the newest finished solution on the device. Every frame
+    keeps the provenance of the chained series; with w = 1 the batched engine is the sequential warm-start chain:
+    frame f starts from frame f - 1's solution, rescaled bitwise, and matches the oracle started from the oracle's
+    previous solution at the fp32 bound of that chain (the emulation chained like the run; restarted from the fp64
+    solution at every frame it leaves out what a chain accumulates: measured on this series, linear e grows from
+    6.7e-8 at frame 0 to 2.5e-7 at frame 22 against a restarted e32 of 5.5e-8, log e is 3.7e-6 from frame 1 on
+    against 3.6e-7, the sequential single-frame engine's chain shows the same, 2.3e-7 and 3.5e-6, and the chained emulation 2.4e-7
+    and 6.5e-6)."""
+    from mpi_cuda_sartsolver_amd.models.laplacian import LaplacianCSR
+    from mpi_cuda_sartsolver_amd.models.multiframe import MultiFrameSARTSolver
+    from mpi_cuda_sartsolver_amd.models.reference import sart_gpu_semantics
+    from mpi_cuda_sartsolver_amd.models.rtm import DenseRTM
+    from mpi_cuda_sartsolver_amd.models.sart import SolverParams
+
+    monkeypatch.setenv("SART_MF_STAGE_WINDOW", str(w))
+    dev = torch.device("cuda", 0)
+    rng = np.random.default_rng(77)
+    P, V, nframes, batch = 600, 1000, 24, 16
+    A = rng.random((P, V), dtype=np.float32)
+    base = rng.random(V) + 0.1
+    X = base[None] * (1.0 + rng.choice([0.01, 0.3], size=(nframes, 1)) * rng.random((nframes, V)))
+    G = X @ A.T.astype(np.float64)
+    L = LaplacianCSR.grid_3d(10, 10, 10, device=dev)
+    kw = dict(max_iterations=60, conv_tolerance=1e-5, beta_laplace=1e-3)
+    s = MultiFrameSARTSolver(DenseRTM.from_dense(A, device=dev), L, None, SolverParams(**kw), logarithmic=log,
+                             batch=batch)
+    x0 = base * 1.5
+    res = s.solve_batch(G, x0=x0, chain=True, record_starts=True)
+    starts, stats = s.starts, s.series_stats
+    assert stats["stage_window"] == w and stats["frames"] == nframes
+    assert all(res[f].warm_from < f for f in range(nframes))
+    check_chain_provenance(res, starts, stats, A, G, L, x0, log, kw)
+    if w != 1:
+        return
+    from fp32_bound import ORDERS, rel
+    from mpi_cuda_sartsolver_amd.models.reference import sart_fp32_emulation
+
+    norm = G.max(axis=1)
+    assert res[0].warm_from == -1
+    # The sequential chain of the oracle itself: each frame from the oracle's previous solution (frame 0 from x0), run
+    # for our recorded update count. Bounded as check_fp32_bound bounds one frame (factor 1, slack 1e-7), by the fp32
+    # emulation of the same chain: the emulation starts each frame from its own previous solution, as every fp32
+    # solver of a sequential series must (tests/test_cli_e2e.py chain_errors(warm=True) bounds the sequential mode
+    # this way); restarted from the fp64 solution at every frame it would leave out what any fp32 chain accumulates.
+    prev64, prev32 = x0, {o: x0 for o in ORDERS}
+    for f in range(nframes):
+        if f >= 1:
+            assert res[f].warm_from == f - 1 and not res[f].warm_live, (f, res[f].warm_from, res[f].warm_live)
+            want = np.maximum((res[f - 1].solution / norm[f]).astype(np.float32), np.float32(1e-7))
+            np.testing.assert_array_equal((starts[f] / norm[f]).astype(np.float32), want)
+        okw = dict(logarithmic=log, max_iterations=res[f].iterations, beta_laplace=1e-3)
+        prev64 = sart_gpu_semantics(A, G[f], L, x_prev=prev64, conv_tolerance=0.0, **okw)[0]
+        prev32 = {o: sart_fp32_emulation(A, G[f], L, x_prev=prev32[o], order=o, **okw)[0] for o in ORDERS}
+        e, e32 = rel(res[f].solution, prev64), max(rel(prev32[o], prev64) for o in ORDERS)
+        assert e <= e32 + 1e-7, f"frame {f}: rel {e:.3e} vs the fp32 emulation of the chain {e32:.3e}"
 
 def test_multiframe_series_iterations_near_sequential():
     """A slowly drifting series (the ray-traced phantom's regime): the pipelined chain keeps the warm start's
