@@ -177,6 +177,7 @@ static void bind_engine(py::module_& m) {
         // row-scaled f16 storage: row_scale is the device pointer of the shard's scale array ([nrows_pad] scales,
         // then [nrows_pad] inverses; the caller keeps it alive with the engine)
         .def_readwrite("rtm_f16", &sart::EngineConfig::rtm_f16)
+        .def_readwrite("f16_fused", &sart::EngineConfig::f16_fused)
         .def_property("row_scale",
                       [](const sart::EngineConfig& c) { return reinterpret_cast<uintptr_t>(c.row_scale); },
                       [](sart::EngineConfig& c, uintptr_t p) { c.row_scale = P<const float>(p); })

@@ -74,6 +74,7 @@ PYBIND11_MODULE(_sart_native, m) {
         .def_readwrite("partition_voxels", &Config::partition_voxels)
         .def_readwrite("rtm_bf16", &Config::rtm_bf16)
         .def_readwrite("rtm_f16", &Config::rtm_f16)
+        .def_readwrite("rtm_f16_fused", &Config::rtm_f16_fused)
         .def_readwrite("rtm_format", &Config::rtm_format)
         .def_readwrite("profile_file", &Config::profile_file)
         .def_readwrite("help", &Config::help);

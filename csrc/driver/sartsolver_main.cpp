@@ -509,7 +509,9 @@ int main(int argc, char** argv) {
             EngineConfig ec;
             static_cast<SolverParams&>(ec) = params;
             ec.conv_tolerance *= tol_factor;
-            ec.use_fused = !cfg.two_pass && !cfg.rtm_f16;  // f16 shards: the two-pass kernels (no fused f16 sweep yet)
+            // f16 shards: the two-pass kernels unless --rtm_f16_fused opts in to the fused f16 sweep
+            ec.f16_fused = cfg.rtm_f16_fused;
+            ec.use_fused = !cfg.two_pass && (!cfg.rtm_f16 || cfg.rtm_f16_fused);
             ec.fused_min_bytes = fused_min_bytes_from_env();
             if (const char* v = std::getenv("SART_FUSED_VARIANT"); v && *v) ec.fused_variant = std::atoi(v);
             ec.time_collectives = !cfg.profile_file.empty();  // --profile: GPU time in the all-reduces per frame

@@ -102,10 +102,13 @@ Engine::Engine(int device, const void* A, int64_t nrows, int64_t nrows_pad, int6
         if (cfg_.column_shard) throw std::invalid_argument("Engine: row-scaled f16 storage is for row shards");
         if (!cfg_.row_scale)
             throw std::invalid_argument("Engine: an f16 shard needs its row scales (EngineConfig::row_scale)");
-        if (cfg_.use_fused)
-            throw std::invalid_argument("Engine: the fused f16 sweep is not built yet; f16 shards run the two-pass "
-                                        "kernels (use_fused = false)");
+        if (cfg_.use_fused && !cfg_.f16_fused)
+            throw std::invalid_argument("Engine: the fused f16 sweep is not built yet into the defaults; f16 shards "
+                                        "run the two-pass kernels (use_fused = false) unless f16_fused / "
+                                        "--rtm_f16_fused opts in to it");
         rinv_ = cfg_.row_scale + Pp_;
+    } else if (cfg_.f16_fused) {
+        throw std::invalid_argument("Engine: f16_fused applies to row-scaled f16 shards (rtm_f16)");
     }
     cfg_.check_interval = std::max(1, cfg_.check_interval);
     if (cfg_.column_shard) {
@@ -163,19 +166,21 @@ Engine::Engine(int device, const void* A, int64_t nrows, int64_t nrows_pad, int6
     if (const char* c = std::getenv("SART_FUSED_CUS"); c && *c && cfg_.fused_max_cus <= 0) cfg_.fused_max_cus = std::atoi(c);
     if (cfg_.fused_max_cus > 0) plan_cus_ = std::min(plan_cus_, cfg_.fused_max_cus);
     plan_cus_ = plan_cus_ / 8 * 8;  // whole CUs per XCD
-    // bf16 storage: the fused sweep exists as variant 6 only (else the two-pass kernels)
-    const double abytes = (double)Pp_ * (double)ld_ * (cfg_.rtm_bf16 ? 2.0 : 4.0);
+    // 16-bit storage (bf16, or f16 with f16_fused): the fused sweep exists as variant 6 only (else the two-pass
+    // kernels), planned alike for both formats (the tiles' bytes are the same)
+    const bool s16 = storage16();
+    const double abytes = (double)Pp_ * (double)ld_ * (s16 ? 2.0 : 4.0);
     if (cfg_.use_fused && !sparse_ && !cfg_.column_shard && abytes >= cfg_.fused_min_bytes && plan_cus_ >= 8 &&
-        (!shared_device_ || fused_ok_shared) && (!cfg_.rtm_bf16 || cfg_.fused_variant == 6)) {
-        geom_ = fused_geometry(ld_, plan_cus_, cfg_.fused_variant, cfg_.rows_per_tile, !cfg_.rtm_bf16, !cfg_.rtm_bf16);
-        if (cfg_.rtm_bf16 && (cfg_.rows_per_tile == 0 || cfg_.rows_per_tile == 4)) {
-            // wide bf16 tiles (8 KB per wave per step, like fp32) where the width allows; SART_BF16_WIDE=0 keeps
+        (!shared_device_ || fused_ok_shared) && (!s16 || cfg_.fused_variant == 6)) {
+        geom_ = fused_geometry(ld_, plan_cus_, cfg_.fused_variant, cfg_.rows_per_tile, !s16, !s16);
+        if (s16 && (cfg_.rows_per_tile == 0 || cfg_.rows_per_tile == 4)) {
+            // wide 16-bit tiles (8 KB per wave per step, like fp32) where the width allows; SART_BF16_WIDE=0 keeps
             // the narrow tiles
             const char* w = std::getenv("SART_BF16_WIDE");
             const FusedGeometry gw = fused_geometry_bf16_wide(ld_, plan_cus_);
             if (gw.valid() && !(w && std::string(w) == "0")) geom_ = gw;
         }
-        use_fused_ = geom_.valid() && (!cfg_.rtm_bf16 || geom_.variant == 6);
+        use_fused_ = geom_.valid() && (!s16 || geom_.variant == 6);
     }
     // Every rank runs the fused sweep or none does: shards of different heights can land on both sides of
     // fused_min_bytes, and a rank on the two-pass kernels would then see its peers' protocol errors (the error
@@ -223,11 +228,22 @@ void Engine::drop_graph() {
 
 void Engine::alloc_fused() {
     nF_fused_ = use_fused_ ? (int64_t)geom_.grid * fused_fpart_per_block(geom_.variant) : 0;
-    const ChainPlan plan = use_fused_ ? fused_chain_plan(geom_, Pp_, fused_split_schedule(geom_.K, cfg_.rtm_bf16))
+    const ChainPlan plan = use_fused_ ? fused_chain_plan(geom_, Pp_, fused_split_schedule(geom_.K, storage16()))
                                       : ChainPlan{};
     chain_tiles_ = plan.chain_tiles;
     fused_blocks_ = use_fused_ ? plan.blocks : 0;
-    const int64_t n_part = std::max<int64_t>(nsplit_, use_fused_ ? fused_blocks_ : 1);
+    int64_t n_part = std::max<int64_t>(nsplit_, use_fused_ ? fused_blocks_ : 1);
+    // Two-level sums of the f16 sweep's partial rows. One chain over all of them (what the tail kernels do) measured
+    // 1.57x the two-pass f16 error at 2048 x 4096 (256 row groups of 8 rows; the bf16 sweep: 1.27x there), over the
+    // project's 1.5x bound. Above 32 rows they are therefore laid out as fold_len_ x fold_runs_ (~sqrt each; the rows
+    // that pad the rectangle are never written and stay zero) and folded by one extra launch per sweep; shards wide
+    // enough to matter for speed have at most 32 row groups (16 at 64k x 64k) and skip it.
+    fold_len_ = fold_runs_ = 0;
+    if (use_fused_ && cfg_.rtm_f16 && fused_blocks_ > 32) {
+        fold_len_ = (int64_t)std::ceil(std::sqrt((double)fused_blocks_));
+        fold_runs_ = (fused_blocks_ + fold_len_ - 1) / fold_len_;
+        n_part = std::max<int64_t>(n_part, fold_len_ * fold_runs_ + fold_runs_);
+    }
     if ((int64_t)partial_.size() < n_part * ld_) partial_.resize(n_part * ld_);
     const int64_t nF = std::max<int64_t>({forward_num_blocks(Pp_), (int64_t)weights_num_blocks(Pp_), nF_fused_, 1});
     if ((int64_t)Fpart_.size() < nF) Fpart_.resize(nF);
@@ -435,7 +451,12 @@ double Engine::setup_frame(const double* g, const double* x0, bool x0_on_device)
         hip_ok(hipMemcpyAsync(x064_.get(), hx0_, V_ * sizeof(double), hipMemcpyHostToDevice, stream_), "H2D x0");
         launch_init_solution(x_.get(), V_, ld_, nullptr, x064_.get(), 1.0 / norm, stream_);
     }
-    if (cfg_.logarithmic) {
+    // The fused f16 sweep sums O itself (below): the log update multiplies by (O + eps) / (A^T (a f) + eps), and with
+    // both sums taken in the same order their roundings largely cancel in the ratio, as they do on the two-pass
+    // kernels. With O from the two-pass back-projection the sweep measured 1.09 - 1.12x the fp32 emulation's error on
+    // the ray-traced 2048 x 4096 model (the two-pass f16 kernels: 0.90 - 0.93x).
+    const bool fused_O = cfg_.logarithmic && use_fused_ && cfg_.rtm_f16;
+    if (cfg_.logarithmic && !fused_O) {
         // frame-constant observed back-projection O = [rho > tau] A^T (a ghat), reduced once per frame
         bwd(wo_.get(), nullptr);
         launch_reduce_partials(partial_.get(), ld_, nsplit_, rs_.dmask.get(), O_.get(), nullptr, 0, nullptr, nullptr,
@@ -443,8 +464,39 @@ double Engine::setup_frame(const double* g, const double* x0, bool x0_on_device)
         if (!cols) comm_->all_reduce(O_.get(), (size_t)ld_, ReduceOp::kSum, stream_);
     }
     launch_state_begin(st_.get(), G, cfg_.conv_tolerance, cfg_.max_iterations, stream_);
-    // per-XCD tickets of the first fused sweep (variant 6); later sweeps get them zeroed by the update kernel
-    if (use_fused_ && geom_.variant == 6) hip_ok(hipMemsetAsync(xcnt_.get(), 0, 16 * sizeof(unsigned), stream_), "memset");
+    auto arm_fused = [&] {
+        // per-XCD tickets of the next fused sweep (variant 6); later sweeps get them zeroed by the update kernel
+        if (use_fused_ && geom_.variant == 6)
+            hip_ok(hipMemsetAsync(xcnt_.get(), 0, 16 * sizeof(unsigned), stream_), "memset");
+    };
+    arm_fused();
+    // the rows that pad the fold rectangle (the set-up's two-pass back-projections may have used them)
+    if (use_fused_ && fold_runs_ > 0 && fold_len_ * fold_runs_ > fused_blocks_)
+        hip_ok(hipMemsetAsync(partial_.get() + fused_blocks_ * ld_, 0,
+                              (size_t)(fold_len_ * fold_runs_ - fused_blocks_) * ld_ * sizeof(float), stream_), "memset");
+    if (fused_O) {
+        // One observed sweep (launch_fused_sweep_f16, observed): it back-projects wo = a max(ghat, 0) / s_p in place of
+        // its own weights, through the sweep's row groups, partial rows and two-level sums. It runs under the frame's
+        // fresh state (not done); its exchange epoch is then retired so that the first iteration's gatherers cannot
+        // take its granules for theirs. A protocol timeout in it stays in SartState::error and stops the frame at the
+        // first sweep's decision, which falls back to the two-pass kernels (and their O) like any other.
+        launch_fused_sweep_f16(true, geom_.K, static_cast<const f16s_t*>(A_), ld_, P_, Pp_, x_.get(), wo_.get(),
+                               arow_.get(), rinv_, partial_.get(), Fpart_.get(), gran_.get(), geom_.I, geom_.J,
+                               st_.get(), xcnt_.get(), stream_, geom_.cpl, chain_tiles_, geom_.kw, geom_.xl, true);
+        const float* part = partial_.get();
+        int nsplit = (int)fused_blocks_;
+        if (fold_runs_ > 0) {
+            float* fold = partial_.get() + fold_len_ * fold_runs_ * ld_;
+            launch_reduce_partials(part, ld_ * fold_runs_, (int)fold_len_, nullptr, fold, nullptr, 0, nullptr, nullptr,
+                                   stream_);
+            part = fold;
+            nsplit = (int)fold_runs_;
+        }
+        launch_reduce_partials(part, ld_, nsplit, rs_.dmask.get(), O_.get(), nullptr, 0, nullptr, nullptr, stream_);
+        if (!cols) comm_->all_reduce(O_.get(), (size_t)ld_, ReduceOp::kSum, stream_);
+        launch_state_next_epoch(st_.get(), stream_);
+        arm_fused();
+    }
     return norm;
 }
 
@@ -457,13 +509,18 @@ void Engine::sweep() {
         return;
     }
     unsigned* xcnt = (use_fused_ && geom_.variant == 6) ? xcnt_.get() : nullptr;  // zeroed by setup / update
-    const int nsplit = use_fused_ ? (int)fused_blocks_ : nsplit_;
+    int nsplit = use_fused_ ? (int)fused_blocks_ : nsplit_;
+    const float* part = partial_.get();
     const int64_t nF = use_fused_ ? nF_fused_ : (sparse_ ? csr_forward_num_blocks(sp_, Pp_) : forward_num_blocks(Pp_));
     // One rank: the reduction of the partial rows, the decision and the update are one kernel (nothing to
     // all-reduce in between); every workgroup sums the nF sweep partials, so only while nF stays small.
     const bool one_tail = tail_fused_ && comm_->size() == 1 && nF <= 4096;
     if (use_fused_) {
-        if (cfg_.rtm_bf16)  // variant 6, K = rows per tile
+        if (cfg_.rtm_f16)  // variant 6 on f16 tiles, the rows' 1 / s_p applied where a tile's row dots are finished
+            launch_fused_sweep_f16(cfg_.logarithmic, geom_.K, static_cast<const f16s_t*>(A_), ld_, P_, Pp_, x_.get(),
+                                   ghat_.get(), arow_.get(), rinv_, partial_.get(), Fpart_.get(), gran_.get(), geom_.I,
+                                   geom_.J, st, xcnt_.get(), stream_, geom_.cpl, chain_tiles_, geom_.kw, geom_.xl);
+        else if (cfg_.rtm_bf16)  // variant 6, K = rows per tile
             launch_fused_sweep_bf16(cfg_.logarithmic, geom_.K, static_cast<const bf16_t*>(A_), ld_, P_, Pp_, x_.get(),
                                     ghat_.get(), arow_.get(), partial_.get(), Fpart_.get(), gran_.get(), geom_.I,
                                     geom_.J, st, xcnt_.get(), stream_, geom_.cpl, chain_tiles_, geom_.kw, geom_.xl);
@@ -474,6 +531,14 @@ void Engine::sweep() {
     } else {
         fwd(cfg_.logarithmic ? kEpiLog : kEpiLinear, x_.get(), nullptr, w_.get(), Fpart_.get(), st);
         bwd(w_.get(), st);
+    }
+    if (use_fused_ && fold_runs_ > 0) {
+        // row r of the fold = rows r, r + fold_runs_, ... of the sweep: the partial rows read as fold_len_ rows of
+        // ld * fold_runs_ floats, summed by the reduction kernel in its fixed order
+        float* fold = partial_.get() + fold_len_ * fold_runs_ * ld_;
+        launch_reduce_partials(part, ld_ * fold_runs_, (int)fold_len_, nullptr, fold, nullptr, 0, nullptr, st, stream_);
+        part = fold;
+        nsplit = (int)fold_runs_;
     }
     const float* pen = nullptr;
     if (has_lap_) {
@@ -495,16 +560,16 @@ void Engine::sweep() {
         u.xprev = xprev_.get();
         u.ticket = ticket_.get();
         u.logmode = cfg_.logarithmic;
-        updated = comm_->reduce_all_reduce_update(ReduceSrc{partial_.get(), ld_, nsplit, scale, Fpart_.get(), nF, st},
+        updated = comm_->reduce_all_reduce_update(ReduceSrc{part, ld_, nsplit, scale, Fpart_.get(), nF, st},
                                                   comm_buf_.get(), u, stream_);
         comm_end();
     } else if (!one_tail) {
-        launch_reduce_partials(partial_.get(), ld_, nsplit, scale, comm_buf_.get(), Fpart_.get(), nF, Fslot, st,
+        launch_reduce_partials(part, ld_, nsplit, scale, comm_buf_.get(), Fpart_.get(), nF, Fslot, st,
                                stream_);
     }
     if (updated) {
     } else if (one_tail)
-        launch_reduce_decide_update(cfg_.logarithmic, st, partial_.get(), ld_, nsplit, scale, Fpart_.get(), nF,
+        launch_reduce_decide_update(cfg_.logarithmic, st, part, ld_, nsplit, scale, Fpart_.get(), nF,
                                     x_.get(), O_.get(), pen, (float)cfg_.relaxation, V_, xcnt, xprev_.get(),
                                     ticket_.get(), stream_);
     else
@@ -620,7 +685,7 @@ bool Engine::fallback() {
     // scratch. A rank whose own kernels are already the two-pass ones re-solves on them: its peers step down
     // their chains and re-solve too, so every rank enters the same number of collectives.
     drop_graph();
-    if (use_fused_ && geom_.variant == 6 && !cfg_.rtm_bf16) {
+    if (use_fused_ && geom_.variant == 6 && !storage16()) {  // (16-bit tiles: variant 6 only)
         const FusedGeometry g3 = fused_geometry(ld_, plan_cus_, 3, 0);
         if (g3.valid()) {
             std::fprintf(stderr, "sart: fused sweep variant 6 timed out (unexpected workgroup placement); using variant 3\n");

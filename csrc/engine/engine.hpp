@@ -70,9 +70,11 @@ struct EngineConfig : SolverParams {
     // scale per row (sart_common.hpp f16s_t; 11 significant bits at bf16's two bytes), row_scale the device array
     // written with the shard by launch_f32_to_f16_rows: [nrows_pad] scales, then [nrows_pad] inverses (not owned).
     // The solve is exact SART for the matrix H / s_p: ray sums are taken over it, every product and sum stays fp32 /
-    // fp64. Two-pass kernels (use_fused must be false: no fused f16 sweep yet) and the f16-storage MFMA multi-frame
-    // kernels; row shards only.
+    // fp64. Two-pass kernels and the f16-storage MFMA multi-frame kernels; row shards only. The fused sweep (variant
+    // 6 on f16 tiles, planned like the bf16 one) is opt-in: use_fused on an f16 shard needs f16_fused, so that the
+    // defaults keep the two-pass kernels until the fused f16 sweep has been measured widely enough to become one.
     bool rtm_f16 = false;
+    bool f16_fused = false;
     const float* row_scale = nullptr;
     // Multi-frame engine with an fp32 shard: run the projections on the bf16 matrix cores with A split into
     // hi + lo bf16 in registers (three products per element; multiframe_bf16.hip, "split-A") instead of fp32
@@ -179,6 +181,7 @@ class Engine {
    private:
     void ray_sums();
     void alloc_fused();
+    bool storage16() const { return cfg_.rtm_bf16 || cfg_.rtm_f16; }  // 2-byte elements (bf16 / row-scaled f16)
     double setup_frame(const double* g, const double* x0, bool x0_on_device = false);
     void sweep();
     void sweep_columns();
@@ -208,6 +211,10 @@ class Engine {
     int64_t nF_fused_ = 0;
     int64_t chain_tiles_ = 0;     // fused sweep chain_tiles (T = 1 fold period / T >= 2 segment length), 0 = off
     int64_t fused_blocks_ = 0;   // partial-sum rows written by the fused sweep (I, or I * T * segments)
+    // f16 fused sweep with many partial rows (narrow shards: up to one row group per CU): the rows are summed in two
+    // levels, fold_len_ rows (stride fold_runs_) into each of fold_runs_ rows behind the sweep's, which the tail then
+    // sums -- chains of ~sqrt(rows) terms instead of one of all rows. 0 runs: off.
+    int64_t fold_len_ = 0, fold_runs_ = 0;
     double norm_ = 1.0;
     int last_sweeps_ = 0;  // sweeps of the previous solve: the first chunk of a warm-started one
     bool last_x_on_device_ = false;  // x_ holds the previous solve's returned solution (no rollback since)

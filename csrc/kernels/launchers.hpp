@@ -129,6 +129,9 @@ void launch_update_linear(float* x, const float* d, const float* pen, int64_t n,
 void launch_update_log(float* x, const float* O, const float* Fv, const float* pen, float alpha, int64_t n,
                        const SartState* st, hipStream_t stream, unsigned* xcnt = nullptr, float* xprev = nullptr);
 void launch_state_begin(SartState* st, double G, double tol, int max_iter, hipStream_t stream);
+// the next exchange epoch without a decision (after a fused sweep run outside the iteration, whose granules must not
+// be taken for the next sweep's); leaves SartState::error for the next sweep's decision
+void launch_state_next_epoch(SartState* st, hipStream_t stream);
 // w = a (ghat - f) (linear) or a f (log) from a complete forward projection f; Fpart[block] = sum f^2 (fp64)
 int weights_num_blocks(int64_t nrows_pad);
 void launch_weights(bool logmode, const float* f, const float* ghat, const float* arow, int64_t nrows,
@@ -179,6 +182,18 @@ void launch_fused_sweep_bf16(bool logmode, int T, const bf16_t* A, int64_t ld, i
                              const float* x, const float* ghat, const float* arow, float* partial, double* Fpart,
                              uint64_t* gran, int I, int J, SartState* st, unsigned* xcnt, hipStream_t stream,
                              int cpl = 4, int64_t chain_tiles = 0, int kw = 8, bool xl = true);
+// fused_sweep_f16.hip: row-scaled f16 RTM (f16s_t), the same sweep on f16 tiles with the bf16 geometry (T, cpl, kw,
+// xl as above). rinv: the rows' 1 / s_p ([nrows_pad], the second half of the shard's scale array), applied where a
+// tile's row dots are finished. Built for the planner's defaults only: wide tiles at T = 4 / 2 (kw 5 ... 8, XCD-local
+// and chip-wide), narrow tiles at kw 8 (T = 1, 2, 4, XCD-local); SART_BF16_T2_SCHED=6 and schedule 5 at T = 1 throw.
+void launch_fused_sweep_f16(bool logmode, int T, const f16s_t* A, int64_t ld, int64_t nrows, int64_t nrows_pad,
+                            const float* x, const float* ghat, const float* arow, const float* rinv, float* partial,
+                            double* Fpart, uint64_t* gran, int I, int J, SartState* st, unsigned* xcnt,
+                            hipStream_t stream, int cpl = 4, int64_t chain_tiles = 0, int kw = 8, bool xl = true,
+                            bool observed = false);
+// observed (log mode): the sweep back-projects the caller's row operand, passed as ghat (a max(ghat, 0) / s_p), in
+// place of the weights it forms from the row dots: partial then holds A^T of that operand in the sweep's own
+// summation order (the log solver's frame-constant O; Fpart is written and meaningless)
 // p2p_allreduce.hip: one-shot push all-reduce through IPC-mapped peer buffers (at most 8 ranks, fp32).
 // Receive buffer of every rank: [2 parities][kP2pMaxRanks sources][cap] floats; flags: [sources][blocks].
 constexpr int kP2pMaxRanks = 8;

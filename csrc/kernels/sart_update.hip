@@ -483,6 +483,15 @@ void launch_update_log(float* x, const float* O, const float* Fv, const float* p
     check_launch("k_update_log");
 }
 
+__global__ void k_state_next_epoch(SartState* __restrict__ st) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) st->epoch = st->epoch + 1;
+}
+
+void launch_state_next_epoch(SartState* st, hipStream_t stream) {
+    hipLaunchKernelGGL(k_state_next_epoch, dim3(1), dim3(64), 0, stream, st);
+    check_launch("k_state_next_epoch");
+}
+
 void launch_state_begin(SartState* st, double G, double tol, int max_iter, hipStream_t stream) {
     hipLaunchKernelGGL(k_state_begin, dim3(1), dim3(64), 0, stream, st, G, tol, max_iter);
     check_launch("k_state_begin");

@@ -91,6 +91,9 @@ std::string usage() {
            "                              (the same two bytes as --rtm_bf16 with 11 significant bits instead of\n"
            "                              8; two-pass kernels, and the matrix cores with --batch_frames).\n"
            "                              Exclusive with --rtm_bf16.\n"
+           "  --rtm_f16_fused             With --rtm_f16: run the fused single-pass sweep on the f16 shard (one\n"
+           "                              read of the RTM per iteration instead of two; opt-in, ignored with\n"
+           "                              --batch_frames; --two_pass still selects the two-pass kernels).\n"
            "  --rtm_format F              auto | dense | sparse: keep a sparse RTM sparse (CSR + CSC; the GPU\n"
            "                              solvers and the CPU solver, pixel-row shards). auto: when every RTM dataset is\n"
            "                              sparse COO with at most 10 % non-zeros. [default: auto]\n"
@@ -122,7 +125,7 @@ Config parse_arguments(const std::vector<std::string>& argv) {
         {"--logarithmic", &c.logarithmic}, {"--no_guess", &c.no_guess},   {"--use_cpu", &c.use_cpu},
         {"--parallel_read", &c.parallel_read}, {"--resume", &c.resume}, {"--two_pass", &c.two_pass},
         {"--partition_voxels", &c.partition_voxels}, {"--rtm_bf16", &c.rtm_bf16},
-        {"--rtm_f16", &c.rtm_f16},
+        {"--rtm_f16", &c.rtm_f16}, {"--rtm_f16_fused", &c.rtm_f16_fused},
     };
     const std::map<std::string, std::string> alias = {
         {"-o", "--output_file"},           {"-t", "--time_range"},          {"-w", "--wavelength_threshold"},
@@ -187,6 +190,7 @@ Config parse_arguments(const std::vector<std::string>& argv) {
         throw Error("Arguments rtm_f16 and rtm_bf16 are exclusive: one storage format per RTM.");
     if (c.rtm_f16 && (c.use_cpu || c.partition_voxels))
         throw Error("Argument rtm_f16 applies to the GPU solvers with pixel-row shards only.");
+    if (c.rtm_f16_fused && !c.rtm_f16) throw Error("Argument rtm_f16_fused needs rtm_f16.");
     if (c.rtm_format != "auto" && c.rtm_format != "dense" && c.rtm_format != "sparse")
         throw Error("Argument rtm_format must be auto, dense or sparse, " + c.rtm_format + " given.");
     if (c.rtm_format == "sparse" && (c.partition_voxels || c.rtm_bf16 || c.rtm_f16 || (c.use_cpu && c.batch_frames > 1)))

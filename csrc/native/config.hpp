@@ -40,6 +40,7 @@ struct Config {
     // dense shard. "auto": when every RTM dataset is sparse COO with at most 10 % non-zeros; "dense" / "sparse".
     std::string rtm_format = "auto";
     bool rtm_f16 = false;       // GPU: store the RTM shard as row-scaled f16 (exclusive with rtm_bf16)
+    bool rtm_f16_fused = false; // GPU, with rtm_f16: run the fused single-pass f16 sweep (opt-in; else two-pass)
     bool rtm_bf16 = false;      // GPU: store the RTM shard in bf16 (fp32 products and sums)  // GPU: shard the RTM by voxel columns (all pixels per rank) instead of pixel rows
     std::string profile_file;   // JSON timing/telemetry sidecar
     bool help = false;

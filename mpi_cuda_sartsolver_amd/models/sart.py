@@ -110,7 +110,8 @@ class SARTSolver:
                  logarithmic: bool = False, use_fused: Optional[bool] = None, check_interval: int = 16,
                  allow_zero_tolerance: bool = False, fused_variant: Optional[int] = None,
                  fused_rows_per_tile: Optional[int] = None, use_graph: Optional[bool] = None,
-                 fused_min_bytes: float = 0.0, partition: Optional[str] = None, time_collectives: bool = False):
+                 fused_min_bytes: float = 0.0, partition: Optional[str] = None, time_collectives: bool = False,
+                 f16_fused: bool = False):
         self.k = hip()
         self.rtm = rtm
         self.dev = rtm.device
@@ -119,14 +120,18 @@ class SARTSolver:
         self.params.validate(allow_zero_tolerance)
         self.log = bool(logarithmic)
         self.L = laplacian if (laplacian is not None and laplacian.nnz > 0 and self.params.beta_laplace > 0) else None
-        # use_fused None: the fused sweep where the engine has one for the shard (every shard but row-scaled f16
-        # ones, which run the two-pass kernels; asking for the fused sweep there is an error)
+        # use_fused None: the fused sweep where the engine runs one by default for the shard (every shard but
+        # row-scaled f16 ones: their fused sweep is opt-in, f16_fused=True, and without it they run the two-pass
+        # kernels; asking for the fused sweep there without the opt-in is an error)
         is_f16 = bool(getattr(rtm, "is_f16", False))
+        f16_fused = bool(f16_fused)
+        if f16_fused and not is_f16:
+            raise ValueError("f16_fused applies to row-scaled f16 shards (DenseRTM(storage='f16'))")
         if use_fused is None:
-            use_fused = not is_f16
-        elif use_fused and is_f16:
-            raise ValueError("the fused f16 sweep is not built yet: f16 shards run the two-pass kernels "
-                             "(use_fused=False or None)")
+            use_fused = f16_fused if is_f16 else True
+        elif use_fused and is_f16 and not f16_fused:
+            raise ValueError("the fused f16 sweep is not built yet into the defaults: f16 shards run the two-pass "
+                             "kernels (use_fused=False or None) unless f16_fused=True opts in to it")
         # "rows" (reference layout) or "cols" (voxel shard); default: from the shard
         if partition not in (None, "rows", "cols"):
             raise ValueError("partition must be 'rows' or 'cols'")
@@ -156,8 +161,9 @@ class SARTSolver:
         cfg.fused_min_bytes = float(fused_min_bytes)  # smaller shards use the two-pass kernels
         cfg.time_collectives = bool(time_collectives)
         cfg.rtm_bf16 = bool(getattr(rtm, "is_bf16", False))  # bf16-stored shard: two-pass kernels  # SolveResult.comm_ms (events around each all-reduce)
-        if is_f16:  # row-scaled f16 shard: two-pass kernels with exact widening, the scales travel with the shard
+        if is_f16:  # row-scaled f16 shard: exact widening, the scales travel with the shard
             cfg.rtm_f16 = True
+            cfg.f16_fused = f16_fused
             cfg.row_scale = rtm.row_scale.data_ptr()
         if self.column_shard:  # all pixel rows of voxels [col_offset, +nvoxel): two-pass, pixel all-reduce
             cfg.column_shard = True

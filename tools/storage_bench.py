@@ -5,8 +5,8 @@
 ray-traced RTM with reflections (utils/raytrace.py; the 64k x 64k matrix of tools/parity_at_scale.py by default) it
 reports, per storage format, as JSON lines:
 
-* single-frame it/s through ``SARTSolver`` on its default path (fused sweep; two-pass kernels for f16) and on the
-  two-pass kernels, and multi-frame frame-it/s through ``MultiFrameSARTSolver`` at each ``--frames`` batch width,
+* single-frame it/s through ``SARTSolver`` on its default path (fused sweep; two-pass kernels for f16), on the
+  two-pass kernels, and for f16 on the opt-in fused sweep (``f16_fused=True``), and multi-frame frame-it/s through ``MultiFrameSARTSolver`` at each ``--frames`` batch width,
   with fixed iterations (``--steps`` updates per solve, tolerance 0, ``--warmup`` untimed solves first), as bench.py;
 * each path's relative error after ``--steps`` updates against the device fp64 oracle (``sart_oracle_f64``) on its
   OWN stored matrix (the arithmetic error of the path) and on the fp32 matrix (arithmetic + storage rounding).
@@ -102,14 +102,17 @@ def main():
                 return dict(err_own_matrix=rel(x, x64_own), err_fp32_matrix=rel(x, x64_fp32))
 
             fused_default = False
-            for name, kw in (("default", {}), ("two_pass", dict(use_fused=False))):
+            paths = [("default", {}), ("two_pass", dict(use_fused=False))]
+            if storage == "f16":
+                paths.append(("f16_fused", dict(f16_fused=True)))  # the opt-in fused f16 sweep, next to the default
+            for name, kw in paths:
                 if name == "two_pass" and not fused_default:
                     continue  # the default path already was the two-pass kernels
                 s = SARTSolver(rtm, None, None, params, logarithmic=log, allow_zero_tolerance=True, **kw)
                 r, sec = timed(lambda: s.solve(G[0]))
                 fused_default = bool(r.used_fused) if name == "default" else fused_default
                 emit(dict(common, path="single-frame " + ("fused" if r.used_fused else "two-pass"), frames=1,
-                          it_per_s=a.steps / sec, ms_per_solve=1e3 * sec,
+                          opt_in=name == "f16_fused", fallbacks=r.fallbacks, it_per_s=a.steps / sec, ms_per_solve=1e3 * sec,
                           rtm_TBps=(1 if r.used_fused else 2) * rtm.nbytes * a.steps / sec / 1e12, **errors(r.solution)))
                 del s
             for nf in widths:
