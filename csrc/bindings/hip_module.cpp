@@ -128,16 +128,18 @@ static void bind_engine(py::module_& m) {
         return std::shared_ptr<sart::Communicator>(sart::comm_from_env(device));
     });
 
+    // (writable and constructible: the planner's tests hand fused_plan geometries fused_geometry never returns)
     py::class_<sart::FusedGeometry>(m, "FusedGeometry")
-        .def_readonly("K", &sart::FusedGeometry::K)
-        .def_readonly("J", &sart::FusedGeometry::J)
-        .def_readonly("I", &sart::FusedGeometry::I)
-        .def_readonly("grid", &sart::FusedGeometry::grid)
-        .def_readonly("variant", &sart::FusedGeometry::variant)
-        .def_readonly("T", &sart::FusedGeometry::T)
-        .def_readonly("cpl", &sart::FusedGeometry::cpl)
-        .def_readonly("kw", &sart::FusedGeometry::kw)
-        .def_readonly("xl", &sart::FusedGeometry::xl)
+        .def(py::init<>())
+        .def_readwrite("K", &sart::FusedGeometry::K)
+        .def_readwrite("J", &sart::FusedGeometry::J)
+        .def_readwrite("I", &sart::FusedGeometry::I)
+        .def_readwrite("grid", &sart::FusedGeometry::grid)
+        .def_readwrite("variant", &sart::FusedGeometry::variant)
+        .def_readwrite("T", &sart::FusedGeometry::T)
+        .def_readwrite("cpl", &sart::FusedGeometry::cpl)
+        .def_readwrite("kw", &sart::FusedGeometry::kw)
+        .def_readwrite("xl", &sart::FusedGeometry::xl)
         .def("valid", &sart::FusedGeometry::valid);
     m.def("fused_geometry", &sart::fused_geometry, py::arg("ld"), py::arg("num_cus"), py::arg("variant") = 6,
           py::arg("rows_per_tile") = 0, py::arg("narrow_slabs") = true, py::arg("chip_wide") = true);
@@ -147,7 +149,33 @@ static void bind_engine(py::module_& m) {
         const auto p = sart::fused_chain_plan(g, nrows_pad, split);
         return py::make_tuple(p.chain_tiles, p.blocks);
     }, py::arg("geometry"), py::arg("nrows_pad"), py::arg("split_schedule"));
-    m.def("fused_split_schedule", &sart::fused_split_schedule, py::arg("T"), py::arg("bf16"));
+    auto fused_key_dict = [](const sart::FusedKey& k) {
+        using namespace pybind11::literals;
+        return py::dict("storage"_a = sart::rtm_storage_name(k.storage), "variant"_a = k.variant, "xl"_a = k.xl,
+                        "diag"_a = k.diag, "T"_a = k.T, "sched"_a = k.sched, "cpl"_a = k.cpl, "kw"_a = k.kw);
+    };
+    // The launch plan of the fused sweep for a geometry and a storage ("f32", "bf16", "f16") under the knobs as they are
+    // now. With ld > 0 also what a launch checks first (fused_check_launch: the shape, then that the kernel is built).
+    m.def("fused_plan", [fused_key_dict](const sart::FusedGeometry& g, const std::string& storage, int64_t ld,
+                                         int64_t nrows_pad, int64_t chain_tiles) {
+        const sart::FusedPlan p = sart::fused_plan(g, sart::rtm_storage_from_name(storage.c_str()),
+                                                   sart::FusedKnobs::current());
+        if (ld > 0) sart::fused_check_launch(p, ld, nrows_pad, g.I, g.J, chain_tiles, true);
+        py::dict d = fused_key_dict(p.key);
+        d["built"] = sart::fused_variant_built(p.key);
+        d["split"] = p.split;
+        d["threads"] = p.threads;
+        d["lds_bytes"] = p.lds_bytes;
+        d["dbg"] = p.dbg;
+        return d;
+    }, py::arg("geometry"), py::arg("storage"), py::arg("ld") = 0, py::arg("nrows_pad") = 0, py::arg("chain_tiles") = 0);
+    // the built kernels of one storage (each exists for both LOG values): the lists of csrc/engine/fused_variants.hpp
+    m.def("fused_variants", [fused_key_dict](const std::string& storage) {
+        py::list out;
+        for (const sart::FusedKey& k : sart::fused_variants(sart::rtm_storage_from_name(storage.c_str())))
+            out.append(fused_key_dict(k));
+        return out;
+    }, py::arg("storage"));
     m.def("choose_ld", &sart::choose_ld, py::arg("nvoxel"), py::arg("max_waste") = 0.10,
           py::arg("narrow_slabs") = true);
 
@@ -745,15 +773,19 @@ PYBIND11_MODULE(_sart_hip, m) {
     m.def("fused_set_trace", [](uintptr_t buf, long long tiles) {
         sart::fused_set_trace(reinterpret_cast<unsigned long long*>(buf), tiles);
     });
-    m.def("fused_fpart_per_block", &sart::fused_fpart_per_block);
     m.def("fused_set_debug", &sart::fused_set_debug);
     m.def("fused_debug_stats", &sart::fused_debug_stats);
+    // one fp32 sweep on 8-KiB slabs in XCD-local row groups (variant 6: K = rows per tile) or variant 3, one chain
     m.def("fused_sweep", [](bool logmode, int K, int variant, uintptr_t A, int64_t ld, int64_t nrows, int64_t nrows_pad,
                             uintptr_t x, uintptr_t ghat, uintptr_t arow, uintptr_t partial, uintptr_t Fpart,
                             uintptr_t gran, int I, int J, uintptr_t st, uintptr_t xcnt, uintptr_t stream) {
-        sart::launch_fused_sweep(logmode, K, variant, P<const float>(A), ld, nrows, nrows_pad, P<const float>(x),
-                                 P<const float>(ghat), P<const float>(arow), P<float>(partial), P<double>(Fpart),
-                                 P<uint64_t>(gran), I, J, P<sart::SartState>(st), P<unsigned>(xcnt), S(stream));
+        sart::FusedGeometry g;
+        g.K = K, g.J = J, g.I = I, g.grid = I * J, g.variant = variant;
+        const sart::FusedArgs a{P<const float>(A), nullptr, ld, nrows, nrows_pad, P<const float>(x), P<const float>(ghat),
+                                P<const float>(arow), P<float>(partial), P<double>(Fpart), P<uint64_t>(gran), I, J,
+                                P<sart::SartState>(st), P<unsigned>(xcnt)};
+        sart::launch_fused_sweep(sart::fused_plan(g, sart::RtmStorage::f32, sart::FusedKnobs::current()), a, logmode,
+                                 S(stream));
     });
     m.def("fused_min_bytes_from_env", &sart::fused_min_bytes_from_env);
     // The multi-frame MFMA projections: every direct kernel call plans from the environment as it is now

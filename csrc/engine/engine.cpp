@@ -83,6 +83,7 @@ Engine::Engine(int device, const void* A, int64_t nrows, int64_t nrows_pad, int6
     if (!comm_) throw std::invalid_argument("Engine: communicator required");
     if (cfg_.rtm_f16 && cfg_.rtm_bf16)
         throw std::invalid_argument("Engine: rtm_f16 and rtm_bf16 are exclusive (one storage format per shard)");
+    storage_ = cfg_.rtm_f16 ? RtmStorage::f16s : (cfg_.rtm_bf16 ? RtmStorage::bf16 : RtmStorage::f32);
     if (sparse) {
         if (cfg_.column_shard || cfg_.rtm_bf16 || cfg_.rtm_f16)
             throw std::invalid_argument("Engine: a sparse shard is a row shard of fp32 values");
@@ -227,8 +228,9 @@ void Engine::drop_graph() {
 }
 
 void Engine::alloc_fused() {
-    nF_fused_ = use_fused_ ? (int64_t)geom_.grid * fused_fpart_per_block(geom_.variant) : 0;
-    const ChainPlan plan = use_fused_ ? fused_chain_plan(geom_, Pp_, fused_split_schedule(geom_.K, storage16()))
+    nF_fused_ = use_fused_ ? geom_.grid : 0;  // one ||A x||^2 partial per workgroup
+    // segments only under a split schedule: the same plan the launches will make, from the knobs as they are now
+    const ChainPlan plan = use_fused_ ? fused_chain_plan(geom_, Pp_, fused_plan(geom_, storage_, FusedKnobs::current()).split)
                                       : ChainPlan{};
     chain_tiles_ = plan.chain_tiles;
     fused_blocks_ = use_fused_ ? plan.blocks : 0;
@@ -475,29 +477,36 @@ double Engine::setup_frame(const double* g, const double* x0, bool x0_on_device)
         hip_ok(hipMemsetAsync(partial_.get() + fused_blocks_ * ld_, 0,
                               (size_t)(fold_len_ * fold_runs_ - fused_blocks_) * ld_ * sizeof(float), stream_), "memset");
     if (fused_O) {
-        // One observed sweep (launch_fused_sweep_f16, observed): it back-projects wo = a max(ghat, 0) / s_p in place of
+        // One observed sweep (FusedArgs::observed): it back-projects wo = a max(ghat, 0) / s_p in place of
         // its own weights, through the sweep's row groups, partial rows and two-level sums. It runs under the frame's
         // fresh state (not done); its exchange epoch is then retired so that the first iteration's gatherers cannot
         // take its granules for theirs. A protocol timeout in it stays in SartState::error and stops the frame at the
         // first sweep's decision, which falls back to the two-pass kernels (and their O) like any other.
-        launch_fused_sweep_f16(true, geom_.K, static_cast<const f16s_t*>(A_), ld_, P_, Pp_, x_.get(), wo_.get(),
-                               arow_.get(), rinv_, partial_.get(), Fpart_.get(), gran_.get(), geom_.I, geom_.J,
-                               st_.get(), xcnt_.get(), stream_, geom_.cpl, chain_tiles_, geom_.kw, geom_.xl, true);
-        const float* part = partial_.get();
-        int nsplit = (int)fused_blocks_;
-        if (fold_runs_ > 0) {
-            float* fold = partial_.get() + fold_len_ * fold_runs_ * ld_;
-            launch_reduce_partials(part, ld_ * fold_runs_, (int)fold_len_, nullptr, fold, nullptr, 0, nullptr, nullptr,
-                                   stream_);
-            part = fold;
-            nsplit = (int)fold_runs_;
-        }
+        fused_sweep(wo_.get(), true);
+        const auto [part, nsplit] = fold_partials(nullptr);
         launch_reduce_partials(part, ld_, nsplit, rs_.dmask.get(), O_.get(), nullptr, 0, nullptr, nullptr, stream_);
         if (!cols) comm_->all_reduce(O_.get(), (size_t)ld_, ReduceOp::kSum, stream_);
         launch_state_next_epoch(st_.get(), stream_);
         arm_fused();
     }
     return norm;
+}
+
+void Engine::fused_sweep(const float* ghat, bool observed) {
+    const FusedArgs a{A_, rinv_, ld_, P_, Pp_, x_.get(), ghat, arow_.get(), partial_.get(), Fpart_.get(), gran_.get(),
+                      geom_.I, geom_.J, st_.get(), xcnt_.get() /* zeroed by setup / update */, chain_tiles_, observed};
+    launch_fused_sweep(fused_plan(geom_, storage_, FusedKnobs::current()), a, cfg_.logarithmic, stream_);
+}
+
+std::pair<const float*, int> Engine::fold_partials(const SartState* st) {
+    if (!use_fused_) return {partial_.get(), nsplit_};
+    if (fold_runs_ == 0) return {partial_.get(), (int)fused_blocks_};
+    // row r of the fold = rows r, r + fold_runs_, ... of the sweep: the partial rows read as fold_len_ rows of
+    // ld * fold_runs_ floats, summed by the reduction kernel in its fixed order
+    float* fold = partial_.get() + fold_len_ * fold_runs_ * ld_;
+    launch_reduce_partials(partial_.get(), ld_ * fold_runs_, (int)fold_len_, nullptr, fold, nullptr, 0, nullptr, st,
+                           stream_);
+    return {fold, (int)fold_runs_};
 }
 
 void Engine::sweep() {
@@ -509,37 +518,17 @@ void Engine::sweep() {
         return;
     }
     unsigned* xcnt = (use_fused_ && geom_.variant == 6) ? xcnt_.get() : nullptr;  // zeroed by setup / update
-    int nsplit = use_fused_ ? (int)fused_blocks_ : nsplit_;
-    const float* part = partial_.get();
     const int64_t nF = use_fused_ ? nF_fused_ : (sparse_ ? csr_forward_num_blocks(sp_, Pp_) : forward_num_blocks(Pp_));
     // One rank: the reduction of the partial rows, the decision and the update are one kernel (nothing to
     // all-reduce in between); every workgroup sums the nF sweep partials, so only while nF stays small.
     const bool one_tail = tail_fused_ && comm_->size() == 1 && nF <= 4096;
     if (use_fused_) {
-        if (cfg_.rtm_f16)  // variant 6 on f16 tiles, the rows' 1 / s_p applied where a tile's row dots are finished
-            launch_fused_sweep_f16(cfg_.logarithmic, geom_.K, static_cast<const f16s_t*>(A_), ld_, P_, Pp_, x_.get(),
-                                   ghat_.get(), arow_.get(), rinv_, partial_.get(), Fpart_.get(), gran_.get(), geom_.I,
-                                   geom_.J, st, xcnt_.get(), stream_, geom_.cpl, chain_tiles_, geom_.kw, geom_.xl);
-        else if (cfg_.rtm_bf16)  // variant 6, K = rows per tile
-            launch_fused_sweep_bf16(cfg_.logarithmic, geom_.K, static_cast<const bf16_t*>(A_), ld_, P_, Pp_, x_.get(),
-                                    ghat_.get(), arow_.get(), partial_.get(), Fpart_.get(), gran_.get(), geom_.I,
-                                    geom_.J, st, xcnt_.get(), stream_, geom_.cpl, chain_tiles_, geom_.kw, geom_.xl);
-        else
-            launch_fused_sweep(cfg_.logarithmic, geom_.K, geom_.variant, static_cast<const float*>(A_), ld_, P_, Pp_,
-                               x_.get(), ghat_.get(), arow_.get(), partial_.get(), Fpart_.get(), gran_.get(), geom_.I,
-                               geom_.J, st, xcnt_.get(), stream_, chain_tiles_, geom_.kw, geom_.xl);
+        fused_sweep(ghat_.get(), false);
     } else {
         fwd(cfg_.logarithmic ? kEpiLog : kEpiLinear, x_.get(), nullptr, w_.get(), Fpart_.get(), st);
         bwd(w_.get(), st);
     }
-    if (use_fused_ && fold_runs_ > 0) {
-        // row r of the fold = rows r, r + fold_runs_, ... of the sweep: the partial rows read as fold_len_ rows of
-        // ld * fold_runs_ floats, summed by the reduction kernel in its fixed order
-        float* fold = partial_.get() + fold_len_ * fold_runs_ * ld_;
-        launch_reduce_partials(part, ld_ * fold_runs_, (int)fold_len_, nullptr, fold, nullptr, 0, nullptr, st, stream_);
-        part = fold;
-        nsplit = (int)fold_runs_;
-    }
+    const auto [part, nsplit] = fold_partials(st);
     const float* pen = nullptr;
     if (has_lap_) {
         launch_penalty(cfg_.logarithmic, lap_rp_.get(), lap_col_.get(), lap_val_.get(), V_, (float)cfg_.beta_laplace,

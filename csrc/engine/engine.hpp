@@ -17,6 +17,7 @@
 
 #include <cstdint>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../kernels/launchers.hpp"
@@ -181,10 +182,16 @@ class Engine {
    private:
     void ray_sums();
     void alloc_fused();
-    bool storage16() const { return cfg_.rtm_bf16 || cfg_.rtm_f16; }  // 2-byte elements (bf16 / row-scaled f16)
+    bool storage16() const { return storage_ != RtmStorage::f32; }  // 2-byte elements (bf16 / row-scaled f16)
     double setup_frame(const double* g, const double* x0, bool x0_on_device = false);
     void sweep();
     void sweep_columns();
+    // One fused sweep on the shard in its storage type, planned from the knobs as they are now. observed (f16 tiles,
+    // log mode): back-projects the row operand passed as ghat in place of the sweep's own weights
+    void fused_sweep(const float* ghat, bool observed);
+    // The partial rows the tail sums and their count: the fused sweep's, folded in two levels first where there are
+    // many (fold_len_ / fold_runs_), else the two-pass back-projection's
+    std::pair<const float*, int> fold_partials(const SartState* st);
     // two-pass kernels on the shard in its storage type: forward (epilogue epi) and split-K back-projection
     // into partial_
     void fwd(int epi, const float* x, float* out_f, float* out_w, double* Fpart, const SartState* st);
@@ -206,6 +213,7 @@ class Engine {
     hipStream_t stream_ = nullptr;
     int num_cus_ = 0;
     bool use_fused_ = false;
+    RtmStorage storage_ = RtmStorage::f32;  // of the dense shard, from cfg_.rtm_bf16 / cfg_.rtm_f16
     FusedGeometry geom_;
     int nsplit_ = 0;
     int64_t nF_fused_ = 0;

@@ -1,27 +1,21 @@
 // Variant 6 of the fused single-pass SART sweep (k_fused_sweep_rows) and its launch wrapper, shared by the
-// translation units that instantiate it: fused_sweep.hip (fp32 and bf16 tiles, with variant 3 and the host-side
-// settings) and fused_sweep_f16.hip (row-scaled f16 tiles). The overview is at the top of fused_sweep.hip.
+// translation units that instantiate it: fused_sweep.hip (fp32 and bf16 tiles, with variant 3 and the launcher) and
+// fused_sweep_f16.hip (row-scaled f16 tiles). The overview is at the top of fused_sweep.hip.
 #pragma once
 
 #include "sart_common.hpp"
 #include "launchers.hpp"
+#include "../engine/fused_variants.hpp"
 
-#include <cstdlib>
 #include <stdexcept>
 #include <type_traits>
 #include <utility>
 
 namespace sart {
 
-constexpr int kFusedThreads = 320;  // 4 compute waves + 1 exchange wave
+// (kFusedThreads, kMaxGather, kRowsGather, sched_split and rows_lds_bytes: engine/fused_plan.hpp, shared with the planner)
 constexpr unsigned kSpinLimit = 1u << 20;
-constexpr int kMaxGather = 512;     // J*T granules per tile
 constexpr int kGatherRegs = kMaxGather / 64;
-constexpr int kRowsGather = 256;    // J*T granules per tile, rows kernel (variant 6)
-
-// Host-side settings kept in fused_sweep.hip, read by launch_rows_t in every translation unit
-int fused_debug_flags();             // fused_set_debug's flags
-void fused_note_schedule(int sched);  // records the SCHED of a variant-6 launch (fused_last_schedule)
 
 // diagnostics (dbg & 2): per-workgroup cycle counters, read with fused_debug_stats(). One copy per translation unit
 // (internal linkage); only the instrumented (DIAG) kernels touch them, and those are all built in fused_sweep.hip.
@@ -293,9 +287,6 @@ __device__ __forceinline__ float class_sum_dpp(float v, int lane) {
 constexpr int t1_reg_slots(int kw) { return kw >= 9 ? 3 : (kw == 8 ? 4 : (kw == 7 ? 5 : (kw == 6 ? 6 : 7))); }
 template <typename AT>
 constexpr bool S16_T() { return !std::is_same<AT, float>::value; }
-
-// Schedules with a separate publisher wave (the split exchange)
-constexpr bool sched_split(int sched) { return sched >= 4 && sched <= 8; }
 
 template <bool LOG, bool XL, bool DIAG, int T, int SCHED, typename AT = float, int CPL = 4, int KW = 8>
 __global__ __launch_bounds__(sched_split(SCHED) ? kFusedThreads + 64 : kFusedThreads) void k_fused_sweep_rows(
@@ -861,11 +852,6 @@ __global__ __launch_bounds__(sched_split(SCHED) ? kFusedThreads + 64 : kFusedThr
     }
 }
 
-constexpr size_t rows_lds_bytes(int T, int sched, int H = 1, int KW = 8) {
-    return (sched == 6 || sched == 7 ? 3 : (sched == 8 ? 5 : 4)) /*NL x 4 waves x KW x 64 lanes x 16 B*/ * 4 * KW * 64 * sizeof(float4) +
-           (((sched >= 1 && sched <= 4) || sched == 6 || sched == 7) ? (4 / T) * KW * 64 * H * sizeof(float4) : 0) +  // x slab
-           (8 * 4 * 3 + 8 + 4) * sizeof(float);
-}
 static_assert(rows_lds_bytes(4, 4, 2) <= 160 * 1024, "wide bf16 tiles: T = 4 fits the LDS");
 static_assert(rows_lds_bytes(2, 6, 2) <= 160 * 1024, "wide bf16 tiles: T = 2 (schedule 6) fits the LDS");
 static_assert(rows_lds_bytes(2, 7, 2) <= 160 * 1024, "wide bf16 tiles: T = 2 (schedule 7) fits the LDS");
@@ -874,36 +860,44 @@ static_assert(rows_lds_bytes(1, 5, 1, 9) <= 160 * 1024, "9-KiB slabs: T = 1 (sch
 static_assert(rows_lds_bytes(1, 8, 1, 7) <= 160 * 1024 && rows_lds_bytes(1, 8, 1, 8) > 160 * 1024,
               "schedule 8: a 5-slot ring of kw 7 slabs fits, of kw 8 slabs not");
 
+// The host side of one instantiation: opts in to its dynamic LDS once (before its first launch, so an engine runs a
+// chunk eagerly before it captures), then launches. dbg: the plan's debug bits (FusedPlan::dbg, | 64 observed).
 template <bool LG, bool X, bool D, int T, int SC, typename AT = float, int CPL = 4, int KW = 8>
 static void launch_rows_t(dim3 grid, hipStream_t stream, const AT* A, int64_t ld, int64_t nrows, int64_t nrows_pad,
                           const float* x, const float* ghat, const float* arow, float* partial, double* Fpart,
                           uint64_t* gran, int I, int J, SartState* st, unsigned* xcnt, int64_t chain_tiles,
-                          const float* rinv = nullptr, int dbg_extra = 0) {
+                          const float* rinv, int dbg) {
     constexpr size_t lds = rows_lds_bytes(T, SC, CPL / 4, KW);
-    fused_note_schedule(SC);
     static bool configured = false;
     if (!configured) {
         hip_call(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_fused_sweep_rows<LG, X, D, T, SC, AT, CPL, KW>),
                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds), "hipFuncSetAttribute");
         configured = true;
     }
-    int dbg = fused_debug_flags() | dbg_extra;
-    if constexpr (X) {
-        const char* gp = std::getenv("SART_FUSED_GPAD");
-        if (gp && *gp && std::atoi(gp) == 2) dbg |= 32;
-    } else {
-        // group map (SART_FUSED_CW_MAP: 0 = b % I, 1 = XCD-balanced, default: balanced for even I only) and granule
-        // padding (SART_FUSED_GPAD=0: unpadded), read per launch (A/B runs)
-        const char* e = std::getenv("SART_FUSED_CW_MAP");
-        const int map = (e && *e) ? std::atoi(e) : 2;
-        if (map == 0 || (map == 2 && I % 2 == 1)) dbg |= 8;
-        const char* gp = std::getenv("SART_FUSED_GPAD");
-        if (gp && *gp && std::atoi(gp) == 0) dbg |= 16;
-    }
     hipLaunchKernelGGL((k_fused_sweep_rows<LG, X, D, T, SC, AT, CPL, KW>), grid,
                        dim3(sched_split(SC) ? kFusedThreads + 64 : kFusedThreads), lds, stream, A, ld, nrows,
                        nrows_pad, x,
                        ghat, arow, partial, Fpart, gran, I, J, st, dbg, xcnt, chain_tiles, rinv);
 }
+
+// Kernel tables (generated from engine/fused_variants.hpp, one per storage type): a key and its launch_rows_t for
+// LOG = false / true
+template <typename AT>
+struct FusedVariant {
+    using Fn = decltype(&launch_rows_t<false, true, false, 4, 4, AT, 4, 8>);
+    FusedKey key;
+    Fn fn[2];
+};
+#define FUSED_ROWS_ENTRY(STORAGE, AT, XL, DIAG, T, SC, CPL, KW)                 \
+    {fused_key(STORAGE, XL, DIAG, T, SC, CPL, KW),                              \
+     {launch_rows_t<false, XL, DIAG, T, SC, AT, CPL, KW>, launch_rows_t<true, XL, DIAG, T, SC, AT, CPL, KW>}},
+template <typename AT, size_t N>
+typename FusedVariant<AT>::Fn fused_variant(const FusedVariant<AT> (&table)[N], const FusedKey& key, bool logmode) {
+    for (const FusedVariant<AT>& v : table)
+        if (v.key == key) return v.fn[logmode];
+    throw std::runtime_error("fused_sweep: the plan's kernel is not in this table");
+}
+// fused_sweep_f16.hip: the lookup in its table
+FusedVariant<f16s_t>::Fn fused_variant_f16(const FusedKey& key, bool logmode);
 
 }  // namespace sart

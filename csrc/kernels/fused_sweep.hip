@@ -31,7 +31,6 @@
 #include "launchers.hpp"
 #include "fused_rows.hpp"
 
-#include <cstdlib>
 #include <stdexcept>
 #include <type_traits>
 #include <utility>
@@ -248,26 +247,12 @@ __global__ __launch_bounds__(kFusedThreads) void k_fused_sweep_lds(
     }
 }
 
-static int g_fused_dbg = 0;    // diagnostics only (set through fused_set_debug)
-static int g_fused_sched = 4;  // variant 6 pipeline schedule (k_fused_sweep_rows SCHED)
-void fused_set_debug(int flags) { g_fused_dbg = flags; }
-int fused_debug_flags() { return g_fused_dbg; }
-void fused_set_schedule(int sched) {
-    if (sched < 0 || sched > 5) throw std::runtime_error("fused_set_schedule: 0 .. 5");
-    g_fused_sched = sched;
-}
-int fused_get_schedule() { return g_fused_sched; }
 static int g_fused_last_sched = -1;  // SCHED of the last k_fused_sweep_rows launch (variant 3: -1)
 int fused_last_schedule() { return g_fused_last_sched; }
-void fused_note_schedule(int sched) { g_fused_last_sched = sched; }
 
 int64_t fused_granules(int64_t nrows_pad, int J, bool xl) {
     (void)xl;  // (XCD-local rows are padded too under SART_FUSED_GPAD=2)
     return nrows_pad * ((J + 15) & ~15);
-}
-bool fused_split_schedule(int T, bool bf16) {  // mirrors the schedule choice of launch_rows / launch_fused_sweep_bf16
-    if (bf16) return T >= 2 || g_fused_sched == 5;
-    return g_fused_sched >= 4;  // T = 1: 4 and 5 both run schedule 5; T >= 2: 5 runs 4
 }
 std::vector<int> fused_debug_map(int nblocks) {
     std::vector<int> out((size_t)nblocks);
@@ -286,12 +271,10 @@ std::vector<unsigned long long> fused_debug_stats(int nblocks) {
 }
 
 
-constexpr size_t kLdsRingBytes = 4 /*NL*/ * 4 /*waves*/ * 8 /*TK*/ * 64 * sizeof(float4) + 160 * sizeof(float);
-
 template <int K>
 static void launch_lds(bool logmode, dim3 grid, hipStream_t stream, const float* A, int64_t ld, int64_t nrows,
                        int64_t nrows_pad, const float* x, const float* ghat, const float* arow, float* partial,
-                       double* Fpart, uint64_t* gran, int I, int J, SartState* st) {
+                       double* Fpart, uint64_t* gran, int I, int J, SartState* st, int dbg) {
     static bool configured = false;
     if (!configured) {  // opt in to > 64 KiB of dynamic LDS once per instantiation
         hip_call(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_fused_sweep_lds<K, true>),
@@ -302,116 +285,34 @@ static void launch_lds(bool logmode, dim3 grid, hipStream_t stream, const float*
     }
     if (logmode)
         hipLaunchKernelGGL((k_fused_sweep_lds<K, true>), grid, dim3(kFusedThreads), kLdsRingBytes, stream, A, ld,
-                           nrows, nrows_pad, x, ghat, arow, partial, Fpart, gran, I, J, st, g_fused_dbg);
+                           nrows, nrows_pad, x, ghat, arow, partial, Fpart, gran, I, J, st, dbg);
     else
         hipLaunchKernelGGL((k_fused_sweep_lds<K, false>), grid, dim3(kFusedThreads), kLdsRingBytes, stream, A, ld,
-                           nrows, nrows_pad, x, ghat, arow, partial, Fpart, gran, I, J, st, g_fused_dbg);
+                           nrows, nrows_pad, x, ghat, arow, partial, Fpart, gran, I, J, st, dbg);
 }
 
-template <int T>
-static void launch_rows(bool logmode, dim3 grid, hipStream_t stream, const float* A, int64_t ld, int64_t nrows,
-                        int64_t nrows_pad, const float* x_, const float* ghat, const float* arow, float* partial,
-                        double* Fpart, uint64_t* gran, int I, int J, SartState* st, unsigned* xcnt,
-                        int64_t chain_tiles, int kw, bool xl) {
-    if (!xl) {
-        // chip-wide row groups (T = 1, schedule 5): workgroup b is (b % I, b / I), granules written through to
-        // memory (agent scope), so a group may span XCDs: J up to the CU count, I = CUs / J of any value
-        if constexpr (T == 1) {
-            auto go_cw = [&](auto lg, auto k, auto sc) {
-                launch_rows_t<decltype(lg)::value, false, false, 1, decltype(sc)::value, float, 4, decltype(k)::value>(
-                    grid, stream, A, ld, nrows, nrows_pad, x_, ghat, arow, partial, Fpart, gran, I, J, st, xcnt,
-                    chain_tiles);
-            };
-            // kw 6 / 7: schedule 8, the deeper exchange pipeline (+5.3 % at 300000 voxels, +2.8 % at 530432,
-            // profiles/ab_r3_cw_sched8.jsonl); SART_FUSED_CW_SCHED=5 keeps schedule 5 (read per launch: A/B runs)
-            const char* cws = std::getenv("SART_FUSED_CW_SCHED");
-            const bool deep = !(cws && std::atoi(cws) == 5);
-            using S5 = std::integral_constant<int, 5>;
-            using S8 = std::integral_constant<int, 8>;
-            auto by_kw = [&](auto lg) {
-                if (kw == 8) go_cw(lg, std::integral_constant<int, 8>{}, S5{});
-                else if (kw == 9) go_cw(lg, std::integral_constant<int, 9>{}, S5{});
-                else if (kw == 7 && deep) go_cw(lg, std::integral_constant<int, 7>{}, S8{});
-                else if (kw == 7) go_cw(lg, std::integral_constant<int, 7>{}, S5{});
-                else if (kw == 6 && deep) go_cw(lg, std::integral_constant<int, 6>{}, S8{});
-                else if (kw == 6) go_cw(lg, std::integral_constant<int, 6>{}, S5{});
-                else go_cw(lg, std::integral_constant<int, 5>{}, S5{});
-            };
-            if (logmode) by_kw(std::true_type{}); else by_kw(std::false_type{});
-            return;
-        } else {
-            // T = 2 / 4 (schedule 4, x slab in LDS): rows of more than an XCD's 32 slabs of 2048 / 4096 columns
-            auto go_cw = [&](auto lg, auto k) {
-                launch_rows_t<decltype(lg)::value, false, false, T, 4, float, 4, decltype(k)::value>(
-                    grid, stream, A, ld, nrows, nrows_pad, x_, ghat, arow, partial, Fpart, gran, I, J, st, xcnt,
-                    chain_tiles);
-            };
-            auto by_kw = [&](auto lg) {
-                if (kw == 8) go_cw(lg, std::integral_constant<int, 8>{});
-                else if (kw == 7) go_cw(lg, std::integral_constant<int, 7>{});
-                else if (kw == 6) go_cw(lg, std::integral_constant<int, 6>{});
-                else throw std::runtime_error("fused_sweep v6: chip-wide T >= 2 needs kw 6 ... 8");
-            };
-            if (logmode) by_kw(std::true_type{}); else by_kw(std::false_type{});
-            return;
-        }
-    }
-    const bool diag = (g_fused_dbg & 2) != 0;  // instrumented build only when asked (timing diagnostics)
-    // g_fused_sched: pipeline schedule (k_fused_sweep_rows SCHED); schedules 1-4 hold the x slab in LDS,
-    // which has room for it only when T >= 2. T = 1 runs schedule 5 (the split exchange with the x slab in
-    // VGPRs) under the default schedule 4 (or 5): +10-14 % over schedule 0 at 73k-262k columns, with and
-    // without idle CUs (profiles/probe_r2_t1_sched5.jsonl); schedules 0-3 select schedule 0 for T = 1.
-    // Instrumented builds: schedules 0, 2 and 4.
-    int sched = T >= 2 ? (g_fused_sched == 5 ? 4 : g_fused_sched) : (g_fused_sched >= 4 ? 5 : 0);
-    if (diag && sched != 2 && sched != 4) sched = 0;
-    auto go = [&](auto lg, auto d, auto sc) {
-        launch_rows_t<decltype(lg)::value, true, decltype(d)::value, T, decltype(sc)::value>(
-            grid, stream, A, ld, nrows, nrows_pad, x_, ghat, arow, partial, Fpart, gran, I, J, st, xcnt, chain_tiles);
-    };
-    using TT = std::true_type;
-    using FF = std::false_type;
-    using S0 = std::integral_constant<int, 0>;
-    using S1 = std::integral_constant<int, (T >= 2 ? 1 : 0)>;
-    using S2 = std::integral_constant<int, (T >= 2 ? 2 : 0)>;
-    using S3 = std::integral_constant<int, (T >= 2 ? 3 : 0)>;
-    using S4 = std::integral_constant<int, (T >= 2 ? 4 : 0)>;
-    using S5 = std::integral_constant<int, (T == 1 ? 5 : 4)>;
-    auto by_log = [&](auto d, auto sc) {
-        if (logmode) go(TT{}, d, sc); else go(FF{}, d, sc);
-    };
-    if (kw != 8) {  // narrower slabs: the default schedules only (4 at T >= 2, 5 at T = 1), no diagnostics
-        auto go_kw = [&](auto lg, auto k) {
-            using SD = std::integral_constant<int, (T >= 2 ? 4 : 5)>;
-            launch_rows_t<decltype(lg)::value, true, false, T, SD::value, float, 4, decltype(k)::value>(
-                grid, stream, A, ld, nrows, nrows_pad, x_, ghat, arow, partial, Fpart, gran, I, J, st, xcnt,
-                chain_tiles);
-        };
-        auto by_kw = [&](auto lg) {
-            if (kw == 7) go_kw(lg, std::integral_constant<int, 7>{});
-            else if (kw == 6) go_kw(lg, std::integral_constant<int, 6>{});
-            else if constexpr (T == 1) {
-                if (kw == 9) go_kw(lg, std::integral_constant<int, 9>{});
-                else go_kw(lg, std::integral_constant<int, 5>{});
-            }
-        };
-        if (logmode) by_kw(TT{}); else by_kw(FF{});
-        return;
-    }
-    if (diag) {
-        if (sched == 2) by_log(TT{}, S2{});
-        else if (sched == 4) by_log(TT{}, S4{});
-        else by_log(TT{}, S0{});
-        return;
-    }
-    switch (sched) {
-        case 1: by_log(FF{}, S1{}); break;
-        case 2: by_log(FF{}, S2{}); break;
-        case 3: by_log(FF{}, S3{}); break;
-        case 4: by_log(FF{}, S4{}); break;
-        case 5: by_log(FF{}, S5{}); break;
-        default: by_log(FF{}, S0{}); break;
-    }
-}
+// The kernel tables, generated from engine/fused_variants.hpp (the f16 one: fused_sweep_f16.hip)
+namespace {
+const FusedVariant<float> kRowsF32[] = {
+#define X(...) FUSED_ROWS_ENTRY(RtmStorage::f32, float, __VA_ARGS__)
+    FUSED_F32_VARIANTS(X)
+#undef X
+};
+const FusedVariant<bf16_t> kRowsBf16[] = {
+#define X(...) FUSED_ROWS_ENTRY(RtmStorage::bf16, bf16_t, __VA_ARGS__)
+    FUSED_BF16_VARIANTS(X)
+#undef X
+};
+struct LdsVariant {
+    FusedKey key;
+    decltype(&launch_lds<8>) fn;
+};
+const LdsVariant kLds[] = {
+#define X(K) {fused_key_v3(K), launch_lds<K>},
+    FUSED_V3_VARIANTS(X)
+#undef X
+};
+}  // namespace
 
 // Variant 3 slab width: 1024 * K columns, K the smallest power of two <= 8 giving at most 32 slabs.
 int fused_pick_k(int64_t ld) {
@@ -423,130 +324,44 @@ int fused_pick_k(int64_t ld) {
     return 8;
 }
 
-int fused_fpart_per_block(int variant) {
-    (void)variant;
-    return 1;
-}
-
 int fused_tile_rows(int K, int variant) {
     return variant == 6 ? K : 8 / K;  // variant 6: K carries the rows per tile; variant 3: 8 float4 per lane
 }
 
-void launch_fused_sweep(bool logmode, int K, int variant, const float* A, int64_t ld, int64_t nrows,
-                        int64_t nrows_pad, const float* x, const float* ghat, const float* arow, float* partial,
-                        double* Fpart, uint64_t* gran, int I, int J, SartState* st, unsigned* xcnt,
-                        hipStream_t stream, int64_t chain_tiles, int kw, bool xl) {
-    if (variant != 3 && variant != 6) throw std::runtime_error("fused_sweep: variant must be 6 or 3");
-    const dim3 grid((unsigned)(I * J));
-    if (variant == 6) {
-        const int T = K;
-        if (T >= 2 && chain_tiles % kChainAlign != 0)
-            throw std::runtime_error("fused_sweep v6: segment length must be a multiple of 140 tiles");
-        if (T != 1 && T != 2 && T != 4) throw std::runtime_error("fused_sweep v6: rows per tile (K) must be 1, 2 or 4");
-        if (kw < 5 || kw > 9) throw std::runtime_error("fused_sweep v6: lane-vectors per lane (kw) must be 5 ... 9");
-        if ((kw == 5 || kw == 9) && T != 1) throw std::runtime_error("fused_sweep v6: 5- and 9-KiB slabs need T = 1");
-        const int64_t slab = 1024 * kw / T;  // columns per workgroup
-        if (ld % slab != 0 || ld / slab != J) throw std::runtime_error("fused_sweep v6: ld must equal J * slab");
-        if (nrows_pad % 4 != 0) throw std::runtime_error("fused_sweep v6: padded rows must be a multiple of 4");
-        if (J * T > kRowsGather) throw std::runtime_error("fused_sweep v6: J * T > 256");
-        if (xl && (xcnt == nullptr || I % 8 != 0))
-            throw std::runtime_error("fused_sweep v6: XCD-local groups need the per-XCD ticket counters and I % 8 == 0");
-        if (!xl && T != 1 && (kw < 6 || kw > 8))
-            throw std::runtime_error("fused_sweep v6: chip-wide row groups at T >= 2 need kw 6 ... 8");
-        if (I < 1) throw std::runtime_error("fused_sweep v6: no row groups");
-        if (T == 1) launch_rows<1>(logmode, grid, stream, A, ld, nrows, nrows_pad, x, ghat, arow, partial, Fpart, gran, I, J, st, xcnt,
-                        chain_tiles, kw, xl);
-        else if (T == 2) launch_rows<2>(logmode, grid, stream, A, ld, nrows, nrows_pad, x, ghat, arow, partial, Fpart, gran, I, J, st, xcnt,
-                        chain_tiles, kw, xl);
-        else launch_rows<4>(logmode, grid, stream, A, ld, nrows, nrows_pad, x, ghat, arow, partial, Fpart, gran, I, J, st, xcnt,
-                        chain_tiles, kw, xl);
-        check_launch("k_fused_sweep_rows");
-        return;
-    }
-    if (K != 1 && K != 2 && K != 4 && K != 8) throw std::runtime_error("fused_sweep v3: K must be 1, 2, 4 or 8");
-    if (ld % (1024 * K) != 0 || ld / (1024 * K) != J) throw std::runtime_error("fused_sweep v3: ld must equal J * 1024 * K");
-    const int T = 8 / K;
-    if (nrows_pad % T != 0) throw std::runtime_error("fused_sweep v3: padded rows must be a multiple of the tile");
-    if (J * T > kMaxGather) throw std::runtime_error("fused_sweep v3: too many slabs for the gather registers");
-    g_fused_last_sched = -1;
-    switch (K) {
-        case 1: launch_lds<1>(logmode, grid, stream, A, ld, nrows, nrows_pad, x, ghat, arow, partial, Fpart, gran, I, J, st); break;
-        case 2: launch_lds<2>(logmode, grid, stream, A, ld, nrows, nrows_pad, x, ghat, arow, partial, Fpart, gran, I, J, st); break;
-        case 4: launch_lds<4>(logmode, grid, stream, A, ld, nrows, nrows_pad, x, ghat, arow, partial, Fpart, gran, I, J, st); break;
-        default: launch_lds<8>(logmode, grid, stream, A, ld, nrows, nrows_pad, x, ghat, arow, partial, Fpart, gran, I, J, st); break;
-    }
-    check_launch("k_fused_sweep_lds");
+// Variant 6 on the tiles of one storage type: the key's table entry, launched on the plan's debug bits
+template <typename AT>
+static void launch_rows(typename FusedVariant<AT>::Fn fn, const FusedPlan& p, const FusedArgs& a, hipStream_t stream) {
+    fn(dim3((unsigned)(a.I * a.J)), stream, static_cast<const AT*>(a.A), a.ld, a.nrows, a.nrows_pad, a.x, a.ghat, a.arow,
+       a.partial, a.Fpart, a.gran, a.I, a.J, a.st, a.xcnt, a.chain_tiles, a.rinv, p.dbg | (a.observed ? 64 : 0));
 }
 
-// bf16-stored RTM: variant 6 only (XCD-local row groups, same exchange as fp32). cpl 8 ("wide": 16-byte loads of
-// 8 bf16 per lane, slab 16384 / T columns) needs T = 4 (schedule 4, x slab in LDS) or T = 2 (schedule 6: a
-// 3-slot ring next to the two sub-slabs' x slab); cpl 4 ("narrow": 8-byte
-// loads, slab 8192 / T) runs schedule 4 for T >= 2 and for T = 1 schedule 0 with the deep bf16 lag (or 5 when
-// selected). A protocol timeout falls back to the bf16 two-pass kernels.
-void launch_fused_sweep_bf16(bool logmode, int T, const bf16_t* A, int64_t ld, int64_t nrows, int64_t nrows_pad,
-                             const float* x, const float* ghat, const float* arow, float* partial, double* Fpart,
-                             uint64_t* gran, int I, int J, SartState* st, unsigned* xcnt, hipStream_t stream, int cpl,
-                             int64_t chain_tiles, int kw, bool xl) {
-    if (T != 1 && T != 2 && T != 4) throw std::runtime_error("fused_sweep bf16: rows per tile must be 1, 2 or 4");
-    if (cpl != 4 && !(cpl == 8 && (T == 4 || T == 2)))
-        throw std::runtime_error("fused_sweep bf16: wide tiles need T = 4 or 2");
-    if (kw != 8 && !(cpl == 8 && kw >= 5 && kw <= 7))
-        throw std::runtime_error("fused_sweep bf16: kw 5 ... 7 only with wide tiles (narrow tiles: kw 8)");
-    if (nrows_pad % 4 != 0) throw std::runtime_error("fused_sweep bf16: padded rows must be a multiple of 4");
-    if (T >= 2 && chain_tiles % kChainAlign != 0)
-        throw std::runtime_error("fused_sweep bf16: segment length must be a multiple of 140 tiles");
-    const int64_t slab = 256 * (int64_t)cpl * kw / T;  // 4 / T sub-slabs of 64 lanes x kw lane-vectors x cpl columns
-    if (ld % slab != 0 || ld / slab != J) throw std::runtime_error("fused_sweep bf16: ld must equal J * slab");
-    if (J * 4 > kMaxGather || J * T > kRowsGather) throw std::runtime_error("fused_sweep bf16: too many slabs");
-    if (xl && (xcnt == nullptr || I % 8 != 0))
-        throw std::runtime_error("fused_sweep bf16: XCD-local groups need ticket counters and I % 8 == 0");
-    if (!xl && cpl != 8) throw std::runtime_error("fused_sweep bf16: chip-wide row groups take the wide tiles only");
-    if (I < 1) throw std::runtime_error("fused_sweep bf16: no row groups");
-    const dim3 grid((unsigned)(I * J));
-    // chip-wide row groups (xl false, wide tiles only): the fp32 chip-wide protocol (granules through memory in
-    // padded rows, the XCD-balanced map) at T = 4 / 2, where a row of 32 wide slabs does not fit one XCD
-    auto go = [&](auto lg, auto tt, auto sc, auto cp) {
-        constexpr int TT = decltype(tt)::value, SC = decltype(sc)::value, CP = decltype(cp)::value;
-        auto run = [&](auto k) {
-            if constexpr (CP == 8) {
-                if (!xl) {
-                    launch_rows_t<decltype(lg)::value, false, false, TT, SC, bf16_t, CP, decltype(k)::value>(
-                        grid, stream, A, ld, nrows, nrows_pad, x, ghat, arow, partial, Fpart, gran, I, J, st, xcnt,
-                        chain_tiles);
-                    return;
-                }
-            }
-            launch_rows_t<decltype(lg)::value, true, false, TT, SC, bf16_t, CP, decltype(k)::value>(
-                grid, stream, A, ld, nrows, nrows_pad, x, ghat, arow, partial, Fpart, gran, I, J, st, xcnt, chain_tiles);
-        };
-        if constexpr (CP == 8) {  // wide tiles: narrower slabs so that J fills an XCD's 32 CUs at more widths
-            if (kw == 7) return run(std::integral_constant<int, 7>{});
-            if (kw == 6) return run(std::integral_constant<int, 6>{});
-            if (kw == 5) return run(std::integral_constant<int, 5>{});
-        }
-        run(std::integral_constant<int, 8>{});
-    };
-    using S0 = std::integral_constant<int, 0>;
-    using S4 = std::integral_constant<int, 4>;
-    using S5 = std::integral_constant<int, 5>;
-    using S6 = std::integral_constant<int, 6>;
-    using S7 = std::integral_constant<int, 7>;
-    // wide tiles at T = 2: schedule 7 (L = 4) unless SART_BF16_T2_SCHED=6 (read per launch: tests switch it)
-    const char* t2e = std::getenv("SART_BF16_T2_SCHED");
-    const bool t2_sched6 = t2e && std::atoi(t2e) == 6;
-    using C4 = std::integral_constant<int, 4>;
-    using C8 = std::integral_constant<int, 8>;
-    auto by_t = [&](auto lg) {
-        if (cpl == 8 && T == 2 && t2_sched6) go(lg, std::integral_constant<int, 2>{}, S6{}, C8{});
-        else if (cpl == 8 && T == 2) go(lg, std::integral_constant<int, 2>{}, S7{}, C8{});
-        else if (cpl == 8) go(lg, std::integral_constant<int, 4>{}, S4{}, C8{});
-        else if (T == 1 && g_fused_sched == 5) go(lg, std::integral_constant<int, 1>{}, S5{}, C4{});
-        else if (T == 1) go(lg, std::integral_constant<int, 1>{}, S0{}, C4{});
-        else if (T == 2) go(lg, std::integral_constant<int, 2>{}, S4{}, C4{});
-        else go(lg, std::integral_constant<int, 4>{}, S4{}, C4{});
-    };
-    if (logmode) by_t(std::true_type{}); else by_t(std::false_type{});
-    check_launch("k_fused_sweep_rows<bf16>");
+void launch_fused_sweep(const FusedPlan& p, const FusedArgs& a, bool logmode, hipStream_t stream) {
+    const FusedKey& k = p.key;
+    if (k.storage == RtmStorage::f16s) {
+        if (a.observed && !logmode) throw std::runtime_error("fused_sweep f16: the observed sweep is a log-mode sweep");
+        if (a.rinv == nullptr) throw std::runtime_error("fused_sweep f16: the rows' inverse scales are required");
+    } else if (a.observed) {
+        throw std::runtime_error("fused_sweep: the observed sweep exists for f16 tiles only");
+    }
+    fused_check_launch(p, a.ld, a.nrows_pad, a.I, a.J, a.chain_tiles, a.xcnt != nullptr);
+    g_fused_last_sched = k.sched;
+    if (k.variant == 3) {
+        for (const LdsVariant& v : kLds)
+            if (v.key == k)
+                v.fn(logmode, dim3((unsigned)(a.I * a.J)), stream, static_cast<const float*>(a.A), a.ld, a.nrows,
+                     a.nrows_pad, a.x, a.ghat, a.arow, a.partial, a.Fpart, a.gran, a.I, a.J, a.st, p.dbg);
+        check_launch("k_fused_sweep_lds");
+    } else if (k.storage == RtmStorage::f32) {
+        launch_rows<float>(fused_variant(kRowsF32, k, logmode), p, a, stream);
+        check_launch("k_fused_sweep_rows");
+    } else if (k.storage == RtmStorage::bf16) {
+        launch_rows<bf16_t>(fused_variant(kRowsBf16, k, logmode), p, a, stream);
+        check_launch("k_fused_sweep_rows<bf16>");
+    } else {
+        launch_rows<f16s_t>(fused_variant_f16(k, logmode), p, a, stream);
+        check_launch("k_fused_sweep_rows<f16>");
+    }
 }
 
 }  // namespace sart
+

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "sart_common.hpp"
+#include "../engine/fused_plan.hpp"
 #include "../engine/mf_plan.hpp"
 
 namespace sart {
@@ -153,47 +154,38 @@ void launch_synth_vector(double* out, int64_t n, int64_t offset, uint64_t seed, 
 // fused_sweep.hip
 int fused_pick_k(int64_t ld);
 int fused_tile_rows(int K, int variant);
-void fused_set_schedule(int sched);
-int fused_get_schedule();
+// pipeline schedule the last variant-6 launch ran (T / kw / chip-wide pick it), -1: v3
 int fused_last_schedule();
 // granule buffer entries (uint64) of a variant-6 sweep: chip-wide groups pad each tile's row to 16 granules
-int64_t fused_granules(int64_t nrows_pad, int J, bool xl);  // pipeline schedule the last variant-6 launch ran (T / kw / chip-wide pick it), -1: v3
+int64_t fused_granules(int64_t nrows_pad, int J, bool xl);
 void fused_set_trace(unsigned long long* buf, long long tiles);
 std::vector<int> fused_debug_map(int nblocks);
-int fused_fpart_per_block(int variant);
-void fused_set_debug(int flags);
 std::vector<unsigned long long> fused_debug_stats(int nblocks);
-void launch_fused_sweep(bool logmode, int K, int variant, const float* A, int64_t ld, int64_t nrows, int64_t nrows_pad,
-                        const float* x, const float* ghat, const float* arow, float* partial, double* Fpart,
-                        uint64_t* gran, int I, int J, SartState* st, unsigned* xcnt, hipStream_t stream,
-                        int64_t chain_tiles = 0, int kw = 8, bool xl = true);
-// kw (variant 6): lane-vectors per lane per row, slab = 1024 kw / T columns (8, or 7 / 6 at the default
-// schedules: widths whose 8-KiB-slab count leaves CUs idle; FusedGeometry::kw).
-// chain_tiles (variant 6; 0 = off): T = 1: every ~chain_tiles tiles a compute wave folds its fp32 back-projection
-// chain into a second register set (two-level sums). T >= 2 with a split schedule (fused_split_schedule): the
-// row groups run in segments of chain_tiles tiles (a multiple of kChainAlign); segment s writes the partial
-// blocks (s * T + row) * I + gi, so partial must hold I * T * segments rows of ld floats (fused_chain_plan).
-constexpr int64_t kChainAlign = 140;  // lcm of the register-slot counts RS (4, 5, 7) of the T >= 2 pipelines
-bool fused_split_schedule(int T, bool bf16);
-// bf16-stored RTM: the variant 6 sweep with bf16 tiles (T = rows per tile of the variant 6 geometry; cpl = bf16
-// columns per lane per k-slot: 4 (8-byte loads, slab 8192 / T) or 8 (16-byte loads at T = 4 / 2, "wide": slab
-// 2048 kw / T with kw = 5 ... 8 lane-vectors per lane, 16384 / T at kw 8))
-void launch_fused_sweep_bf16(bool logmode, int T, const bf16_t* A, int64_t ld, int64_t nrows, int64_t nrows_pad,
-                             const float* x, const float* ghat, const float* arow, float* partial, double* Fpart,
-                             uint64_t* gran, int I, int J, SartState* st, unsigned* xcnt, hipStream_t stream,
-                             int cpl = 4, int64_t chain_tiles = 0, int kw = 8, bool xl = true);
-// fused_sweep_f16.hip: row-scaled f16 RTM (f16s_t), the same sweep on f16 tiles with the bf16 geometry (T, cpl, kw,
-// xl as above). rinv: the rows' 1 / s_p ([nrows_pad], the second half of the shard's scale array), applied where a
-// tile's row dots are finished. Built for the planner's defaults only: wide tiles at T = 4 / 2 (kw 5 ... 8, XCD-local
-// and chip-wide), narrow tiles at kw 8 (T = 1, 2, 4, XCD-local); SART_BF16_T2_SCHED=6 and schedule 5 at T = 1 throw.
-void launch_fused_sweep_f16(bool logmode, int T, const f16s_t* A, int64_t ld, int64_t nrows, int64_t nrows_pad,
-                            const float* x, const float* ghat, const float* arow, const float* rinv, float* partial,
-                            double* Fpart, uint64_t* gran, int I, int J, SartState* st, unsigned* xcnt,
-                            hipStream_t stream, int cpl = 4, int64_t chain_tiles = 0, int kw = 8, bool xl = true,
-                            bool observed = false);
-// observed (log mode): the sweep back-projects the caller's row operand, passed as ghat (a max(ghat, 0) / s_p), in
-// place of the weights it forms from the row dots: partial then holds A^T of that operand in the sweep's own
-// summation order (the log solver's frame-constant O; Fpart is written and meaningless)
+// The operands of one fused sweep; the kernel, its threads, LDS and debug bits are the plan's (engine/fused_plan.hpp:
+// fused_plan of the geometry, the storage and FusedKnobs::current(), which also holds fused_set_schedule / _debug).
+struct FusedArgs {
+    const void* A = nullptr;      // the shard in the plan's storage: float, bf16_t or f16s_t, [nrows_pad][ld]
+    const float* rinv = nullptr;  // f16 tiles: the rows' 1 / s_p, applied where a tile's row dots are finished
+    int64_t ld = 0, nrows = 0, nrows_pad = 0;
+    const float *x = nullptr, *ghat = nullptr, *arow = nullptr;
+    float* partial = nullptr;     // I rows of ld floats, or I * T * segments (fused_chain_plan)
+    double* Fpart = nullptr;      // one ||A x||^2 partial per workgroup
+    uint64_t* gran = nullptr;     // fused_granules
+    int I = 0, J = 0;             // row groups x column slabs = the persistent grid
+    SartState* st = nullptr;
+    unsigned* xcnt = nullptr;     // per-XCD ticket counters (XCD-local row groups), zero before every sweep
+    // variant 6; 0 = off. T = 1: every ~chain_tiles tiles a compute wave folds its fp32 back-projection chain into a
+    // second register set (two-level sums). T >= 2 with a split schedule (FusedPlan::split): the row groups run in
+    // segments of chain_tiles tiles (a multiple of kChainAlign); segment s writes the partial blocks
+    // (s * T + row) * I + gi, so partial must hold I * T * segments rows of ld floats
+    int64_t chain_tiles = 0;
+    // f16 tiles, log mode: the sweep back-projects the caller's row operand, passed as ghat (a max(ghat, 0) / s_p), in
+    // place of the weights it forms from the row dots: partial then holds A^T of that operand in the sweep's own
+    // summation order (the log solver's frame-constant O; Fpart is written and meaningless)
+    bool observed = false;
+};
+// Checks the shape against the plan (fused_check_launch: a key whose kernel is not built throws here) and launches.
+void launch_fused_sweep(const FusedPlan& p, const FusedArgs& a, bool logmode, hipStream_t stream);
 // p2p_allreduce.hip: one-shot push all-reduce through IPC-mapped peer buffers (at most 8 ranks, fp32).
 // Receive buffer of every rank: [2 parities][kP2pMaxRanks sources][cap] floats; flags: [sources][blocks].
 constexpr int kP2pMaxRanks = 8;

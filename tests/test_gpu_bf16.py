@@ -277,8 +277,10 @@ def test_bf16_wide_t2_schedules_agree(dev, monkeypatch, log):
         monkeypatch.setenv("SART_BF16_T2_SCHED", sched)
         s = SARTSolver(prob.rtm, None, None, p, logarithmic=log, allow_zero_tolerance=True)
         assert s.use_fused and (s.geom.cpl, s.geom.T) == (8, 2)
+        planned = s.k.fused_plan(s.geom, "bf16")["sched"]
         r = s.solve(g)
         assert r.used_fused and r.fallbacks == 0
+        assert s.k.fused_last_schedule() == planned == int(sched)
         out[sched] = r.solution
         del s
     np.testing.assert_array_equal(out["7"], out["6"])

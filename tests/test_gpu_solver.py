@@ -228,10 +228,13 @@ def test_fused_v6_schedules(dev, T, sched, log):
         s = SARTSolver(DenseRTM.from_dense(A, device=dev), None, None, SolverParams(**kw), logarithmic=log,
                        allow_zero_tolerance=True, fused_variant=6, fused_rows_per_tile=T)
         assert s.geom.variant == 6 and s.geom.T == T
+        planned = k.fused_plan(s.geom, "f32")["sched"]  # the CPU planner (test_fused_plan.py pins it per pair)
         r = s.solve(g)
+        ran = k.fused_last_schedule()
     finally:
         k.fused_set_schedule(prev)
     assert r.used_fused, "fused exchange timed out"
+    assert ran == planned, (ran, planned)
     _check(r.solution, A, g, log=log, max_iterations=10)
 
 
