@@ -52,6 +52,78 @@ static py::dict solve_info(const sart::SolveInfo& i) {
     return d;
 }
 
+// The multi-frame plans as dicts (mf_plan_forward / mf_plan_backproject / mf_engine_plan, MultiFrameEngine.plan)
+static py::dict mf_key_dict(const sart::MfKey& k) {
+    py::dict d;
+    d["path"] = sart::mf_path_name(k.path);
+    d["forward"] = k.forward;
+    d["ng"] = k.ng;
+    d["depth"] = k.depth;
+    d["tile"] = k.tile;
+    d["kb"] = k.kb;
+    d["lds"] = k.lds;
+    d["as"] = k.as;
+    d["early"] = k.early;
+    d["nt"] = k.nt;
+    d["mw"] = k.mw;
+    return d;
+}
+
+static py::dict mf_fwd_plan_dict(const sart::MfFwdPlan& p) {
+    py::dict d = mf_key_dict(p.key);
+    d["nsplit"] = p.nsplit;
+    d["cps"] = p.cps;
+    d["grid"] = py::make_tuple(p.grid_x, p.nsplit);
+    return d;
+}
+
+static py::dict mf_bwd_plan_dict(const sart::MfBwdPlan& p) {
+    py::dict d = mf_key_dict(p.key);
+    d["nsplit"] = p.nsplit;
+    d["rps"] = p.rps;
+    d["vox_align"] = p.vox_align;
+    d["grid"] = py::make_tuple(p.grid_x(0, p.ld), p.nsplit);
+    return d;
+}
+
+static py::dict mf_engine_plan_dict(const sart::MfEnginePlan& p) {
+    py::dict d;
+    d["storage"] = sart::rtm_storage_name(p.storage);
+    d["sparse"] = p.sparse;
+    d["nf"] = p.nf;
+    d["split_a"] = p.split_a;
+    d["fwd"] = p.sparse ? py::object(py::none()) : py::object(py::str(sart::mf_path_name(p.fwd)));
+    d["bwd"] = p.sparse ? py::object(py::none()) : py::object(py::str(sart::mf_path_name(p.bwd)));
+    d["forward_split"] = p.forward_split();
+    d["backproject_split"] = p.backproject_split();
+    d["xblk"] = p.xblk;
+    d["fplan"] = p.sparse ? py::object(py::none()) : py::object(mf_fwd_plan_dict(p.fplan));
+    d["bplan"] = p.sparse ? py::object(py::none()) : py::object(mf_bwd_plan_dict(p.bplan));
+    d["nsf"] = p.nsf;
+    d["nsb"] = p.nsb;
+    d["nwb"] = p.nwb;
+    d["pw"] = p.pw;
+    d["needs_w_planes"] = p.needs_w_planes;
+    d["qcap"] = p.qcap;
+    d["rcap"] = p.rcap;
+    d["chunk"] = p.chunk;
+    d["admit_cap"] = p.admit_cap;
+    d["src_age"] = p.src_age;
+    d["src_finished"] = p.src_finished;
+    d["lead"] = p.lead;
+    d["src_extrap"] = p.src_extrap;
+    d["drift"] = p.drift;
+    d["stage_window"] = p.stage_window;
+    d["skip_last_bwd"] = p.skip_last_bwd;
+    d["use_graph"] = p.use_graph;
+    d["fault_nan"] = p.fault_nan;
+    d["vox_align"] = p.vox_align;
+    d["chunks"] = py::cast(p.chunks);
+    d["collectives"] = py::cast(p.collectives);
+    d["describe"] = p.describe();
+    return d;
+}
+
 static void bind_engine(py::module_& m) {
     py::enum_<sart::ReduceOp>(m, "ReduceOp", py::module_local()).value("SUM", sart::ReduceOp::kSum).value("MAX", sart::ReduceOp::kMax);
     py::class_<sart::Communicator, std::shared_ptr<sart::Communicator>>(m, "Comm")
@@ -337,6 +409,7 @@ static void bind_engine(py::module_& m) {
                         }
                     },
                     py::keep_alive<0, 11>())
+        .def_property_readonly("plan", [](const sart::MultiFrameEngine& e) { return mf_engine_plan_dict(e.plan()); })
         .def_property_readonly("sparse", &sart::MultiFrameEngine::sparse)
         .def_property_readonly("batch_frames", &sart::MultiFrameEngine::batch_frames)
         .def_property_readonly("split_a", &sart::MultiFrameEngine::split_a)
@@ -798,41 +871,26 @@ PYBIND11_MODULE(_sart_hip, m) {
     m.def("mf_backproject_b16_num_splits", &sart::mf_backproject_b16_num_splits, py::arg("ld"), py::arg("nrows"),
           py::arg("a32") = false);
     m.def("mf_backproject_b16_vox_align", &sart::mf_backproject_b16_vox_align, py::arg("ld"), py::arg("a32") = false);
-    auto key_dict = [](const sart::MfKey& k) {
-        py::dict d;
-        d["path"] = sart::mf_path_name(k.path);
-        d["forward"] = k.forward;
-        d["ng"] = k.ng;
-        d["depth"] = k.depth;
-        d["tile"] = k.tile;
-        d["kb"] = k.kb;
-        d["lds"] = k.lds;
-        d["as"] = k.as;
-        d["early"] = k.early;
-        d["nt"] = k.nt;
-        d["mw"] = k.mw;
-        return d;
-    };
+    auto key_dict = &mf_key_dict;
     // path: "fp32", "b16", "x3", "h16" or "s16"; nsplit 0: the planner's split count (what the engine allocates for)
-    m.def("mf_plan_forward", [key_dict](const std::string& path, int nf, int64_t ld, int64_t nrows_pad, int nsplit) {
-        const sart::MfFwdPlan p = sart::mf_plan_forward(sart::mf_path_from_name(path), nf, ld, nrows_pad,
-                                                        sart::MfKnobs::from_env(), nsplit);
-        py::dict d = key_dict(p.key);
-        d["nsplit"] = p.nsplit;
-        d["cps"] = p.cps;
-        d["grid"] = py::make_tuple(p.grid_x, p.nsplit);
-        return d;
+    m.def("mf_plan_forward", [](const std::string& path, int nf, int64_t ld, int64_t nrows_pad, int nsplit) {
+        return mf_fwd_plan_dict(sart::mf_plan_forward(sart::mf_path_from_name(path), nf, ld, nrows_pad,
+                                                      sart::MfKnobs::from_env(), nsplit));
     }, py::arg("path"), py::arg("nf"), py::arg("ld"), py::arg("nrows_pad"), py::arg("nsplit") = 0);
-    m.def("mf_plan_backproject", [key_dict](const std::string& path, int nf, int64_t ld, int64_t nrows, int nsplit) {
-        const sart::MfBwdPlan p = sart::mf_plan_backproject(sart::mf_path_from_name(path), nf, ld, nrows,
-                                                            sart::MfKnobs::from_env(), nsplit);
-        py::dict d = key_dict(p.key);
-        d["nsplit"] = p.nsplit;
-        d["rps"] = p.rps;
-        d["vox_align"] = p.vox_align;
-        d["grid"] = py::make_tuple(p.grid_x(0, ld), p.nsplit);
-        return d;
+    m.def("mf_plan_backproject", [](const std::string& path, int nf, int64_t ld, int64_t nrows, int nsplit) {
+        return mf_bwd_plan_dict(sart::mf_plan_backproject(sart::mf_path_from_name(path), nf, ld, nrows,
+                                                          sart::MfKnobs::from_env(), nsplit));
     }, py::arg("path"), py::arg("nf"), py::arg("ld"), py::arg("nrows"), py::arg("nsplit") = 0);
+    // The engine plan of a shard under the environment as it is now (MfEngineKnobs::from_env, MfKnobs::from_env): what
+    // a MultiFrameEngine built on the same inputs holds (MultiFrameEngine.plan). storage: "f32", "bf16" or "f16".
+    m.def("mf_engine_plan", [](const std::string& storage, bool sparse, int64_t nnz, int frames, int64_t nrows,
+                               int64_t nrows_pad, int64_t ld, int ranks, int mf_split_a, int check_interval) {
+        return mf_engine_plan_dict(sart::mf_engine_plan(sart::rtm_storage_from_name(storage.c_str()), sparse, nnz,
+                                                        frames, nrows, nrows_pad, ld, ranks, mf_split_a,
+                                                        check_interval, sart::MfEngineKnobs::from_env()));
+    }, py::arg("storage"), py::arg("sparse"), py::arg("nnz"), py::arg("frames"), py::arg("nrows"),
+       py::arg("nrows_pad"), py::arg("ld"), py::arg("ranks") = 1, py::arg("mf_split_a") = -1,
+       py::arg("check_interval") = 16);
     // the variant table's keys of one path and direction, each with the knob setting ("env") that selects it
     m.def("mf_variants", [key_dict](const std::string& path, int nf, bool forward) {
         py::list out;

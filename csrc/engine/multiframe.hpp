@@ -20,7 +20,7 @@
 #include "../native/solver_params.hpp"
 #include "comm.hpp"
 #include "engine.hpp"
-#include "mf_plan.hpp"
+#include "mf_engine_plan.hpp"
 
 namespace sart {
 
@@ -63,6 +63,7 @@ class MultiFrameEngine {
         // host time of the series thread: waiting for the GPU (chunk / copy events), staging frames (of which in
         // the source callback: reading), delivering finished frames (de-normalisation and the sink)
         double host_wait_ms = 0.0, host_stage_ms = 0.0, host_src_ms = 0.0, host_deliver_ms = 0.0;
+        // the plan's chain policy as this series ran it (admit_cap, drift and lead apply to a chain only)
         int chunk = 0, admit_cap = 0, src_age = 0, restarts = 0;
         bool src_finished = false, lead = false;
         double src_extrap = 0.0;
@@ -72,18 +73,19 @@ class MultiFrameEngine {
     const SeriesStats& series_stats() const { return stats_; }
     int64_t nrows() const { return P_; }
     int64_t nvoxel() const { return V_; }
-    int batch_frames() const { return nf_; }
-    bool split_a() const { return x3_; }  // fp32 shard on the bf16 matrix cores
-    bool sparse() const { return sparse_; }
-    // the operand pieces of the split-A projections ("f16x2" range-safe f16 pairs, "bf16x2" / "bf16x3" bf16 pieces),
-    // "fp32" (fp32 MFMA) or "bf16-storage"
-    std::string forward_split() const;
-    std::string backproject_split() const;
-    // 16, 32, 64 or 128: the smallest batch width that holds `frames` (128 for anything larger; the constructor
-    // takes 64 where the path has no 128-column kernels)
-    static int batch_width(int frames);
+    // everything decided at construction (mf_engine_plan.hpp); the accessors below read it
+    const MfEnginePlan& plan() const { return plan_; }
+    int batch_frames() const { return plan_.nf; }
+    bool split_a() const { return plan_.split_a; }  // fp32 shard on the 16-bit matrix cores
+    bool sparse() const { return plan_.sparse; }
+    std::string forward_split() const { return plan_.forward_split(); }
+    std::string backproject_split() const { return plan_.backproject_split(); }
+    static int batch_width(int frames) { return mf_batch_width(frames); }
 
    private:
+    // the constructor's argument checks, then the plan under the environment as it is now
+    static MfEnginePlan checked_plan(const void* A, int64_t nrows, int64_t nrows_pad, int64_t nvoxel, int64_t ld,
+                                     Communicator* comm, const EngineConfig& cfg, const SparseRtm* sparse);
     // one pass over frames [first, nframes) (frames already delivered are solved again but not re-delivered);
     // true when a device all-reduce failed on some rank (agreed over the host communicator)
     bool series_once(int64_t first, int64_t nframes, const FrameSource& src, const FrameSink& sink, const double* x0,
@@ -97,9 +99,11 @@ class MultiFrameEngine {
     // frames' pixel columns. The final sweep of a frame decided at max_iter skips its back-projection (q->skip_bwd:
     // reference sartsolver_cuda.cpp:231-262 runs max_iter back-projections after the initial guess)
     void sweep();
-    void refill();  // the plan, start values and pixel columns without a sweep (the first admissions)
-    // chunk_ sweeps: replayed from a HIP graph captured after one eager chunk (one rank, no fault injection;
-    // re-captured when the refill buffers change; SART_MF_GRAPH=0: eager launches)
+    // the decision + refill plan, the update and the admitted frames' pixel columns; without a sweep before it (every
+    // slot done: pen null, the plan only) these are the first admissions
+    void decide_update_admit(const float* pen);
+    // plan_.chunk sweeps: replayed from a HIP graph captured after one eager chunk (one rank, no fault injection;
+    // re-captured when the refill buffers change; plan_.use_graph)
     void run_chunk();
     void drop_graph();
     void set_device() const;
@@ -115,63 +119,45 @@ class MultiFrameEngine {
 
     int device_;
     const void* A_;
-    bool sparse_ = false;
     SparseRtm sp_{};
-    DeviceArray<float> Xt_;  // sparse: X voxel-major planes [nf / PW][ld][PW] for the row gathers
-    DeviceArray<float> Wt_;  // sparse: W as frame-order planes [nf / PW][rows][PW] (launch_mf_w_planes)
-    int pw_ = 64;            // sparse: frames per SpMM plane (mf_sparse_plane_width, fixed at construction)
-    bool bf16_ = false;
-    // row-scaled f16 storage (EngineConfig::rtm_f16, MfPath::s16): the bf16-storage kernels on the f16 MFMA; X / W
-    // pieces as on the f16-pair path (Xh_ / Xl_, W16_, xinv_, wscale_), W with the rows' 1 / s_p folded in (Ws_)
-    bool f16_ = false;
-    DeviceArray<float> Ws_;
-    bool x3_ = false;     // fp32 shard on the bf16 matrix cores (EngineConfig::mf_split_a)
-    bool split_ = false;  // X / W enter as hi + lo bf16 planes (bf16_ || x3_)
-    bool xblk_ = false;   // X planes blocked [ld / 32][nf][32] (launch_mf_split_x / forward xblk)
     int64_t P_, Pp_, V_, ld_;
     Communicator* comm_;
     EngineConfig cfg_;
+    const MfEnginePlan plan_;  // paths, batch width, launch plans, capacities, policy: decided once, executed below
+    DeviceArray<float> Xt_;  // sparse: X voxel-major planes [nf / PW][ld][PW] for the row gathers
+    DeviceArray<float> Wt_;  // sparse: W as frame-order planes [nf / PW][rows][PW] (launch_mf_w_planes)
+    // row-scaled f16 storage (MfPath::s16): the bf16-storage kernels on the f16 MFMA; X / W pieces as on the f16-pair
+    // path (Xh_ / Xl_, W16_, xinv_, wscale_), W with the rows' 1 / s_p folded in (Ws_)
+    DeviceArray<float> Ws_;
     hipStream_t stream_ = nullptr;
-    int nf_ = 16;
-    MfFwdPlan fplan_;  // the projections' launch plans, made once in the constructor (dense shards)
-    MfBwdPlan bplan_;
-    int nsf_ = 1, nsb_ = 1, nwb_ = 1;
     DeviceRaySums rs_;
     DeviceArray<float> X_, Xprev_, Fs_, W_, part_, buf_, pen_, O_, ghat_, arow_, gpos_, wo_;
     DeviceArray<double> G64_, F2part_, x064_;
-    DeviceArray<bf16_t> Xh_, Xl_, Wh_, Wl_;  // bf16 / split-A engine: hi / lo operand planes
-    // split-A back-projection on f16 pairs (launch_mf_backproject_h16): planes w1 | w2 ([2][nf][Pp] f16 bits),
-    // per-frame max scratch and 1 / s_f, and the per-column power-of-two scales of the shard (csc_: [2][ld])
-    bool h16_ = false;
+    DeviceArray<bf16_t> Xh_, Xl_, Wh_, Wl_;  // 16-bit operand paths: hi / lo operand planes
+    // f16 pieces of W (MfPath::h16 and s16 back-projections): planes w1 | w2 ([2][nf][Pp] f16 bits), per-frame max
+    // scratch and 1 / s_f, and for h16 the per-column power-of-two scales of the shard (csc_: [2][ld])
     DeviceArray<bf16_t> W16_;
     DeviceArray<unsigned> wmax_;
     DeviceArray<float> wscale_, csc_;
-    // split-A forward on f16 pairs (launch_mf_forward_h16, default with split-A; SART_MF_FWD16=0: bf16 hi + lo
-    // pieces): X planes in Xh_ / Xl_ (f16 bits), per-row scales of the shard (rsc_: [2][Pp]), per-frame 1 / s_f
-    bool fwd16_ = false;
+    // f16 pieces of X (MfPath::h16 and s16 forwards): X planes in Xh_ / Xl_ (f16 bits), per-frame 1 / s_f, and for
+    // h16 the per-row scales of the shard (rsc_: [2][Pp])
     DeviceArray<float> rsc_, xinv_;
+    uint16_t *x1_ = nullptr, *x2_ = nullptr, *w1_ = nullptr, *w2_ = nullptr;  // the f16 bits of Xh_ / Xl_ / W16_
     DeviceArray<unsigned> xmax_;
     DeviceArray<MfState> st_;
     DeviceArray<int64_t> lap_rp_;
     DeviceArray<int32_t> lap_col_;
     DeviceArray<float> lap_val_;
     bool has_lap_ = false;
-    // overlapped back-projection / all-reduce (several ranks): voxel chunk bounds, comm stream, events
-    std::vector<int64_t> chunks_;
+    // overlapped back-projection / all-reduce (several ranks, plan_.chunks): comm stream, events
     hipStream_t comm_stream_ = nullptr;
     std::vector<hipEvent_t> cev_;
     hipEvent_t comm_done_ = nullptr;
     // device refill: queue (normalised pixels ghq_ [qcap][Pp], cold starts x0q_ / observed back-projections oq_
     // [qcap][ld] when staged), output ring ring_ [rcap][ld], xlast_ [ld], and the plan state q_
-    int qcap_ = 32, rcap_ = 32, chunk_ = 4, admit_cap_ = 0, src_age_ = 0;
-    bool src_finished_ = false, lead_ = true;
     hipGraphExec_t graph_ = nullptr;
     MfRefill graph_rf_{};
-    int graph_chunk_ = 0;
-    bool use_graph_ = true, graph_failed_ = false, warm_chunk_ = false;
-    double src_extrap_ = 0.0;
-    int stage_window_ = 0;  // entry e is staged only while e < finished frames + window (0: no limit)
-    double drift_ = 0.0;  // drift-extrapolated chain starts (MfQueue::drift; SART_MF_DRIFT)
+    bool graph_failed_ = false, warm_chunk_ = false;
     DeviceArray<MfQueue> q_;
     DeviceArray<float> ghq_, x0q_, oq_, ring_, xlast_, xlast2_, starts_;
     MfRefill rf_{};
@@ -187,7 +173,6 @@ class MultiFrameEngine {
     float* hx_ = nullptr;        // pinned [rcap][ld]: solutions of finished frames (D2H target)
     hipStream_t copy_stream_ = nullptr;
     hipEvent_t ev_copy_ = nullptr, ev_stage_ = nullptr;
-    bool skip_last_bwd_ = true;  // SART_MF_LAST_BWD=1: run the final sweep's back-projection anyway (A/B)
     int host_sweep_ = 0;         // sweeps queued in the current series (EngineConfig::fault_nan_sweep)
     SeriesStats stats_;
 };

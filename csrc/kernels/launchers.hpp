@@ -83,10 +83,7 @@ void launch_csc_backproject(const SparseRtm& s, int64_t nvoxel, const float* w, 
 // W[p][f] for v in [v0, v1) (columns >= nvoxel written 0; times scale[v] when given). W: the back-projection
 // layout of launch_mf_weights ([wrows][nf], mf_bp_slot), or with mf_sparse_needs_w_planes(nf, pw) the frame-order
 // planes [nf / PW][wrows][PW] (launch_mf_w_planes, or launch_mf_weights with wplane = PW).
-// frames per SpMM plane for an nf-frame batch (64, or nf below; SART_MF_SPARSE_PW = 16 / 32 / 64 overrides): read
-// once by the engine, which lays X and W out for it
-int mf_sparse_plane_width(int nf);
-bool mf_sparse_needs_w_planes(int nf, int pw);
+// pw and the W layout are the engine plan's (engine/mf_engine_plan.hpp), which lays X and W out for them
 void launch_mf_sparse_forward(const SparseRtm& s, int64_t nrows, int64_t nrows_pad, const float* X, int64_t ld,
                               float* Xt, float* Fout, int nf, int pw, hipStream_t stream, const int* skip);
 void launch_mf_sparse_backproject(const SparseRtm& s, int64_t nvoxel, const float* W, int64_t wrows, float* part,

@@ -16,6 +16,7 @@
 // order, so the engine's reduction, all-reduce, decision and update kernels are shared with the dense path.
 #include "sart_common.hpp"
 #include "launchers.hpp"
+#include "../engine/mf_engine_plan.hpp"  // mf_sparse_needs_w_planes: the engine plan's rule
 
 #include <cstdlib>
 #include <stdexcept>
@@ -125,19 +126,6 @@ static void check_sparse(const SparseRtm& s, const char* what) {
 // coalesced load. fp32 fma chains in entry order per lane. A batch of nf > PW frames runs as nf / PW planes of PW
 // frames (grid.y): a launch then gathers from the working set of one plane (the interleaved [n][128] rows of a
 // 128-frame batch ran at 83.1k frame-it/s, two 64-frame planes at 183k; mf_sparse_plane_width).
-
-int mf_sparse_plane_width(int nf) {
-    int pw = 64;
-    if (const char* e = std::getenv("SART_MF_SPARSE_PW"); e && *e) pw = std::atoi(e);
-    if (pw != 16 && pw != 32 && pw != 64) throw std::runtime_error("SART_MF_SPARSE_PW must be 16, 32 or 64");
-    return nf < pw ? nf : pw;
-}
-
-// The back-projection reads W in its slot layout only for one plane of <= 32 frames: there the 16 lanes of each quarter
-// wave (one pass of the address path) still touch a single 128-B line. At 64 frames the slot order spreads them over
-// the whole 256-B row, twice the lines per gather (113.5k against 183.5k frame-it/s per 64-frame plane,
-// profiles/sparse_r5_plane_width.txt), so W is re-laid in frame order first (launch_mf_w_planes).
-bool mf_sparse_needs_w_planes(int nf, int pw) { return pw < nf || pw > 32; }
 
 static void check_pw(int nf, int pw, const char* what) {
     if ((pw != 16 && pw != 32 && pw != 64) || pw > nf || nf % pw != 0)

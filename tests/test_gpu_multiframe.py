@@ -368,3 +368,59 @@ def test_engine_plans_once(monkeypatch, storage, batch, split_a):
         assert np.array_equal(x, ref[i]), i
         x0 = x[0]
     assert not np.array_equal(ref[0], ref[5])
+
+
+@pytest.fixture(scope="module")
+def plan_shard():
+    rng = np.random.default_rng(7)
+    return rng.random((700, 1000), dtype=np.float32)
+
+
+@pytest.mark.parametrize("storage,batch,env", [
+    ("fp32", 16, {}),
+    ("fp32", 32, {}),
+    ("fp32", 64, {"SART_MF_FWD16": "0", "SART_MF_BWD16": "0"}),
+    ("bf16", 128, {}),
+    ("f16", 128, {}),
+    ("sparse", 128, {}),
+])
+def test_engine_holds_the_plan(monkeypatch, plan_shard, storage, batch, env):
+    """A live engine's plan is mf_engine_plan() of the same shard, configuration and environment, and the accessors
+    and the series statistics read it (700 x 1000, ld 1024; every storage, the split-A default and both bf16-piece
+    paths)."""
+    from mpi_cuda_sartsolver_amd.models.multiframe import MultiFrameSARTSolver
+    from mpi_cuda_sartsolver_amd.models.rtm import DenseRTM, SparseRTM
+    from mpi_cuda_sartsolver_amd.models.sart import SolverParams
+
+    for name in ("SART_MF_X3", "SART_MF_FWD16", "SART_MF_BWD16", "SART_MF_XBLK", "SART_MF_SPARSE_PW", "SART_MF_CHUNK"):
+        monkeypatch.delenv(name, raising=False)
+    for name, val in env.items():
+        monkeypatch.setenv(name, val)
+    dev = torch.device("cuda", 0)
+    A = plan_shard
+    rtm = SparseRTM.from_dense(A, device=dev) if storage == "sparse" else DenseRTM.from_dense(A, device=dev,
+                                                                                                storage=storage)
+    s = MultiFrameSARTSolver(rtm, None, None, SolverParams(max_iterations=3, conv_tolerance=0.0), batch=batch,
+                             check_interval=5, allow_zero_tolerance=True)
+    e, k = s.engine, s.k
+    sparse = storage == "sparse"
+    want = k.mf_engine_plan({"fp32": "f32", "sparse": "f32"}.get(storage, storage), sparse,
+                            int(rtm.nnz) if sparse else 0, batch, 700, 704, 1024, ranks=1, mf_split_a=-1,
+                            check_interval=5)
+    plan = e.plan
+    assert plan == want
+    names = {("fp32", 16): ("fp32", "fp32"), ("fp32", 32): ("f16x2", "f16x2"), ("fp32", 64): ("bf16x2", "bf16x3"),
+             ("bf16", 128): ("bf16-storage",) * 2, ("f16", 128): ("f16-storage",) * 2,
+             ("sparse", 128): ("sparse-fp32",) * 2}[storage, batch]
+    assert (e.batch_frames, e.sparse) == (plan["nf"], plan["sparse"]) == (batch, sparse)
+    assert e.split_a == plan["split_a"] == (storage == "fp32" and batch >= 32)
+    assert (e.forward_split, e.backproject_split) == (plan["forward_split"], plan["backproject_split"]) == names
+    assert (s.batch_width, s.split_a, s.forward_split, s.backproject_split) == (batch, e.split_a, *names)
+    G = (np.random.default_rng(1).random((3, 1000)) + 0.05) @ A.T.astype(np.float64)
+    for chain in (False, True):
+        assert all(r.iterations == 3 for r in s.solve_batch(G, chain=chain))
+        st = s.series_stats
+        assert (st["chunk"], st["src_age"], st["src_finished"], st["src_extrap"], st["stage_window"]) == (
+            plan["chunk"], plan["src_age"], plan["src_finished"], plan["src_extrap"], plan["stage_window"])
+        assert (st["admit_cap"], st["drift"], st["lead"]) == (
+            (plan["admit_cap"], plan["drift"], plan["lead"]) if chain else (0, 0.0, False))
