@@ -17,6 +17,7 @@
 
 #include "../engine/comm.hpp"
 #include "../engine/engine.hpp"
+#include "../engine/engine64.hpp"
 #include "../engine/geometry.hpp"
 #include "../engine/multiframe.hpp"
 #include "../kernels/launchers.hpp"
@@ -376,6 +377,61 @@ static void bind_engine(py::module_& m) {
         .def_property_readonly("stream", [](const sart::Engine& e) { return reinterpret_cast<uintptr_t>(e.stream()); })
         .def("ray_density", [](const sart::Engine& e) { auto v = e.ray_density(); return py::array_t<double>(v.size(), v.data()); })
         .def("ray_length", [](const sart::Engine& e) { auto v = e.ray_length(); return py::array_t<double>(v.size(), v.data()); })        ;
+
+    // The double-precision engine (fp32 dense row shards; cfg's storage / partition flags and `sparse` describe the
+    // shard offered, and anything else is refused). gpu_semantics as CpuSolver's flag
+    py::class_<sart::Engine64>(m, "Engine64")
+        .def(py::init([](int device, uintptr_t A, int64_t nrows, int64_t nrows_pad, int64_t nvoxel, int64_t ld,
+                         std::shared_ptr<sart::Communicator> comm, const sart::EngineConfig& cfg, bool gpu_semantics,
+                         bool sparse) {
+                 try {
+                     const sart::SparseRtm s{};
+                     return new sart::Engine64(device, P<const float>(A), nrows, nrows_pad, nvoxel, ld, comm.get(), cfg,
+                                               gpu_semantics, sparse ? &s : nullptr);
+                 } catch (const std::invalid_argument& e) {
+                     throw py::value_error(e.what());
+                 }
+             }),
+             py::arg("device"), py::arg("A"), py::arg("nrows"), py::arg("nrows_pad"), py::arg("nvoxel"), py::arg("ld"),
+             py::arg("comm"), py::arg("cfg"), py::arg("gpu_semantics") = true, py::arg("sparse") = false,
+             py::keep_alive<1, 8>())
+        .def("set_laplacian",
+             [](sart::Engine64& e, py::array_t<int64_t, py::array::c_style | py::array::forcecast> rp,
+                py::array_t<int32_t, py::array::c_style | py::array::forcecast> col,
+                py::array_t<float, py::array::c_style | py::array::forcecast> val) {
+                 e.set_laplacian(rp.data(), col.data(), val.data(), (int64_t)val.size());
+             })
+        .def("solve",
+             [](sart::Engine64& e, f64arr g, py::object x0) {
+                 if ((int64_t)g.size() != e.nrows())
+                     throw py::value_error("measurement has " + std::to_string(g.size()) +
+                                           " pixels, the local shard has " + std::to_string(e.nrows()));
+                 f64arr x0a;
+                 const double* x0p = nullptr;
+                 if (!x0.is_none()) {
+                     x0a = x0.cast<f64arr>();
+                     if ((int64_t)x0a.size() != e.nvoxel())
+                         throw py::value_error("Solution vector must be empty or contain nvoxel elements.");
+                     x0p = x0a.data();
+                 }
+                 py::array_t<double> x(e.nvoxel());
+                 double* xp = x.mutable_data();
+                 const double* gp = g.data();
+                 sart::SolveInfo info;
+                 {
+                     py::gil_scoped_release rel;
+                     info = e.solve(gp, x0p, xp);
+                 }
+                 return py::make_tuple(x, solve_info(info));
+             },
+             py::arg("g"), py::arg("x0") = py::none())
+        .def_property_readonly("gpu_semantics", &sart::Engine64::gpu_semantics)
+        .def_property_readonly("num_cus", &sart::Engine64::num_cus)
+        .def_property_readonly("nrows", &sart::Engine64::nrows)
+        .def_property_readonly("nvoxel", &sart::Engine64::nvoxel)
+        .def_property_readonly("stream", [](const sart::Engine64& e) { return reinterpret_cast<uintptr_t>(e.stream()); })
+        .def("ray_density", [](const sart::Engine64& e) { auto v = e.ray_density(); return py::array_t<double>(v.size(), v.data()); })
+        .def("ray_length", [](const sart::Engine64& e) { auto v = e.ray_length(); return py::array_t<double>(v.size(), v.data()); });
 
     py::class_<sart::MultiFrameEngine>(m, "MultiFrameEngine")
         .def(py::init([](int device, uintptr_t A, int64_t nrows, int64_t nrows_pad, int64_t nvoxel, int64_t ld,
@@ -793,6 +849,25 @@ PYBIND11_MODULE(_sart_hip, m) {
     m.def("reduce_partials_f64", [](uintptr_t partial, int64_t ld, int nsplit, uintptr_t out, uintptr_t stream) {
         sart::launch_reduce_partials_f64(P<const double>(partial), ld, nsplit, P<double>(out), S(stream));
     });
+    // projection64.hip: the fp64 two-pass kernels (fp32 shard, fp64 vectors)
+    m.def("forward64", [](int epi, uintptr_t A, int64_t ld, int64_t nrows, int64_t nrows_pad, int64_t nvoxel,
+                          uintptr_t x, uintptr_t g, uintptr_t arow, uintptr_t out_f, uintptr_t out_w, uintptr_t Fpart,
+                          uintptr_t st, uintptr_t stream) {
+        sart::launch_forward64(epi, P<const float>(A), ld, nrows, nrows_pad, nvoxel, P<const double>(x),
+                               P<const double>(g), P<const double>(arow), P<double>(out_f), P<double>(out_w),
+                               P<double>(Fpart), P<const sart::SartState>(st), S(stream));
+    }, py::arg("epi"), py::arg("A"), py::arg("ld"), py::arg("nrows"), py::arg("nrows_pad"), py::arg("nvoxel"),
+       py::arg("x"), py::arg("g"), py::arg("arow"), py::arg("out_f"), py::arg("out_w"), py::arg("Fpart"),
+       py::arg("st") = 0, py::arg("stream") = 0);
+    m.def("sum_f64", [](uintptr_t v, int64_t n, uintptr_t out, uintptr_t st, uintptr_t stream) {
+        sart::launch_sum_f64(P<const double>(v), n, P<double>(out), P<const sart::SartState>(st), S(stream));
+    }, py::arg("v"), py::arg("n"), py::arg("out"), py::arg("st") = 0, py::arg("stream") = 0);
+    m.def("backproject64", [](uintptr_t A, int64_t ld, int64_t nrows, uintptr_t w, int nsplit, uintptr_t partial,
+                              uintptr_t st, uintptr_t stream) {
+        sart::launch_backproject64(P<const float>(A), ld, nrows, P<const double>(w), nsplit, P<double>(partial),
+                                   P<const sart::SartState>(st), S(stream));
+    }, py::arg("A"), py::arg("ld"), py::arg("nrows"), py::arg("w"), py::arg("nsplit"), py::arg("partial"),
+       py::arg("st") = 0, py::arg("stream") = 0);
     m.def("prep_rows", [](uintptr_t g, int64_t nrows, int64_t nrows_pad, double inv_s, uintptr_t ray_length,
                           float len_thres, uintptr_t ghat, uintptr_t arow, uintptr_t gpos, uintptr_t wo,
                           uintptr_t stream) {

@@ -76,6 +76,8 @@ PYBIND11_MODULE(_sart_native, m) {
         .def_readwrite("rtm_f16", &Config::rtm_f16)
         .def_readwrite("rtm_f16_fused", &Config::rtm_f16_fused)
         .def_readwrite("rtm_format", &Config::rtm_format)
+        .def_readwrite("fp64", &Config::fp64)
+        .def_readwrite("fp64_semantics", &Config::fp64_semantics)
         .def_readwrite("profile_file", &Config::profile_file)
         .def_readwrite("help", &Config::help);
     m.def("parse_arguments", &parse_arguments, py::arg("argv"));

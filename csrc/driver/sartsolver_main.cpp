@@ -45,6 +45,7 @@
 
 #include "../engine/comm.hpp"
 #include "../engine/engine.hpp"
+#include "../engine/engine64.hpp"
 #include "../engine/geometry.hpp"
 #include "../engine/multiframe.hpp"
 #include "../kernels/launchers.hpp"
@@ -454,7 +455,8 @@ int main(int argc, char** argv) {
         // --rtm_format: the single-frame GPU solver on pixel-row shards of fp32 values can keep a sparse RTM sparse
         // (decided from the files' metadata: the same on every rank)
         bool sparse = false;
-        if (!cols && !cfg.rtm_bf16 && !cfg.rtm_f16 && cfg.rtm_format != "dense") {
+        // (--fp64 reads dense shards: auto loads the matrix dense)
+        if (!cols && !cfg.rtm_bf16 && !cfg.rtm_f16 && !cfg.fp64 && cfg.rtm_format != "dense") {
             const double dens = rtm_sparse_density(in.rtm_files, in.rtm_name, in.npixel, in.nvoxel);
             // auto: the sparse kernels read 16 bytes per non-zero and sweep (CSR + CSC, index + value) against 4 bytes
             // per element for the dense fused sweep; measured at 32768 x 32768 (uniform random positions): sparse /
@@ -535,6 +537,7 @@ int main(int argc, char** argv) {
             return e;
         };
         std::unique_ptr<Engine> engine, lead_engine;
+        std::unique_ptr<Engine64> engine64;  // --fp64: the double-precision engine, frame by frame
         // the lead frame stops at lead_tol x the tolerance and hands its iterate to the batch, where it finishes next
         // to the frames chained from it (1: it finishes on the single-frame engine; SART_MF_LEAD_TOL)
         double lead_tol = 1.0;
@@ -563,6 +566,12 @@ int main(int argc, char** argv) {
             const char* le = std::getenv("SART_MF_LEAD_ENGINE");
             if (const char* lt = std::getenv("SART_MF_LEAD_TOL"); lt && *lt) lead_tol = std::max(1.0, std::atof(lt));
             if (!cfg.no_guess && !(le && *le && std::atoi(le) == 0)) lead_engine = make_engine(lead_tol);
+        } else if (gpu && cfg.fp64) {
+            EngineConfig ec;
+            static_cast<SolverParams&>(ec) = params;
+            engine64 = std::make_unique<Engine64>(device, dshard->A, dshard->nrows, dshard->nrows_pad, dshard->nvoxel,
+                                                  dshard->ld, dcomm.get(), ec, cfg.fp64_semantics == "gpu");
+            if (lap.nnz()) engine64->set_laplacian(lap.row_ptr.data(), lap.col.data(), lap.val.data(), lap.nnz());
         } else if (gpu) {
             engine = make_engine(1.0);
         } else {
@@ -619,6 +628,8 @@ int main(int argc, char** argv) {
             std::string path = "cpu";
             if (mf)
                 path = "multi-frame " + mf->forward_split() + " / " + mf->backproject_split();
+            else if (engine64)
+                path = "fp64-two-pass";
             else if (engine)
                 path = sparse ? "sparse two-pass" : (engine->use_fused() ? "fused" : "two-pass");
             if (profile.is_open())
@@ -647,6 +658,7 @@ int main(int argc, char** argv) {
                         << ", \"rtm_storage\": \"" << storage << "\", \"f16_flushed\": " << (uint64_t)fl[0]
                         << ", \"f16_flushed_fraction\": " << (fl[1] > 0 ? fl[0] / fl[1] : 0.0)
                         << ", \"solver_path\": \"" << json_escape(path) << "\""
+                        << (engine64 ? ", \"fp64_semantics\": \"" + cfg.fp64_semantics + "\"" : std::string())
                         << ", \"nnz\": " << (sparse ? (gpu ? sshard->nnz : cpu_nnz) : 0) << ", \"driver\": \"native\"}\n";
         }
 
@@ -862,8 +874,9 @@ int main(int argc, char** argv) {
             const double* x0 = (cfg.no_guess || solution.empty()) ? nullptr : solution.data();
             // from frame 1 on, a warm start is the engine's own previous solution: rescaled on the device
             // (SART_WARM_ON_DEVICE=0: through the host copy, for A/B runs)
-            const SolveInfo info = gpu ? engine->solve(frame.data(), x0, x.data(), k > 0 && x0 != nullptr && warm_dev)
-                                       : cpu->solve(frame.data(), x0, x.data());
+            const SolveInfo info = engine64 ? engine64->solve(frame.data(), x0, x.data())
+                                   : gpu    ? engine->solve(frame.data(), x0, x.data(), k > 0 && x0 != nullptr && warm_dev)
+                                            : cpu->solve(frame.data(), x0, x.data());
             if (info.fallbacks)
                 std::cerr << "warning: fused sweep fell back " << info.fallbacks << " time(s)" << std::endl;
             if (info.comm_fallbacks && rank == 0)

@@ -99,6 +99,35 @@ void launch_f32_to_bf16(const float* src, int64_t n, bf16_t* dst, hipStream_t st
 void launch_reduce_partials(const float* partial, int64_t ld, int nsplit, const float* scale, float* out,
                             const double* Fpart, int64_t nF, float* Fout, const SartState* st, hipStream_t stream);
 void launch_reduce_partials_f64(const double* partial, int64_t ld, int nsplit, double* out, hipStream_t stream);
+// projection64.hip: the double-precision two-pass kernels of Engine64 (fp32 shard [nrows_pad][ld], fp64 vectors, fp64
+// FMAs; no atomics). st (optional unless noted): the launch returns at once when st->done.
+// f = A x (x: ld doubles, entries at and beyond nvoxel are not used) with the epilogues of launch_forward: epi 0 f only,
+// 1 out_w = arow (g - f), 2 out_w = arow f; rows >= nrows are neither read from g / arow nor written. Fpart (optional):
+// forward_num_blocks(nrows_pad) fp64 partial sums of f^2 (launch_sum_f64 adds them)
+void launch_forward64(int epi, const float* A, int64_t ld, int64_t nrows, int64_t nrows_pad, int64_t nvoxel,
+                      const double* x, const double* g, const double* arow, double* out_f, double* out_w,
+                      double* Fpart, const SartState* st, hipStream_t stream);
+// out[0] = sum v[0, n), fixed order
+void launch_sum_f64(const double* v, int64_t n, double* out, const SartState* st, hipStream_t stream);
+// partial[s][c] = sum over the rows of split s of A[p][c] w[p] for c < ld (written, also by empty splits);
+// launch_reduce_partials_f64 sums the nsplit rows. w beyond nrows is not read
+void launch_backproject64(const float* A, int64_t ld, int64_t nrows, const double* w, int nsplit, double* partial,
+                          const SartState* st, hipStream_t stream);
+// x[i] = valid[i] ? src[i] / rho_s[i] : 0 (valid given: cold start) or src[i] / div, then max(x, clamp) when
+// clamp > 0; x[n, n_pad) = 0
+void launch_init_x64(double* x, int64_t n, int64_t n_pad, const double* src, const int32_t* valid, const double* rho_s,
+                     double div, double clamp, hipStream_t stream);
+void launch_mask64(double* v, const int32_t* valid, int64_t n, hipStream_t stream);  // v[i] = 0 where !valid[i]
+// pen = beta L x (or beta L log x), each row summed in CSR order
+void launch_penalty64(bool logx, const int64_t* row_ptr, const int32_t* col, const float* val, int64_t n, double beta,
+                      const double* x, double* pen, const SartState* st, hipStream_t stream);
+// The stopping rule of CpuSolver::solve on the device state: Fslot[0] = sum f^2 of the sweep, over all ranks
+void launch_decide64(SartState* st, const double* Fslot, hipStream_t stream);
+// CpuSolver::solve's update (linear: red the reduced back-projection; log: red = A^T (a f), O the observed one);
+// gpu_semantics selects max(x, 0) over the signbit test. pen optional. st required
+void launch_update64(bool logmode, double* x, const double* red, const double* O, const double* pen,
+                     const int32_t* valid, const double* rho_s, double alpha, double eps, bool gpu_semantics, int64_t n,
+                     const SartState* st, hipStream_t stream);
 // sart_update.hip
 void launch_prep_rows(const double* g, int64_t nrows, int64_t nrows_pad, double inv_s, const float* ray_length,
                       float len_thres, float* ghat, float* arow, float* gpos, float* wo, hipStream_t stream);

@@ -97,11 +97,18 @@ std::string usage() {
            "  --rtm_format F              auto | dense | sparse: keep a sparse RTM sparse (CSR + CSC; the GPU\n"
            "                              solvers and the CPU solver, pixel-row shards). auto: when every RTM dataset is\n"
            "                              sparse COO with at most 10 % non-zeros. [default: auto]\n"
+           "  --fp64                      Solve on the GPU in double precision (fp32 RTM, every vector, product and\n"
+           "                              sum fp64; two reads of the RTM per iteration): the answer to compare the\n"
+           "                              other precisions against. Frame by frame, dense pixel-row shards.\n"
+           "  --fp64_semantics S          gpu | cpu, with --fp64. gpu: the default GPU path (normalisation,\n"
+           "                              epsilon 1e-7, fp32-rounded thresholds) evaluated in fp64; cpu: what\n"
+           "                              --use_cpu computes. [default: gpu]\n"
            "  --profile FILE              Write per-frame timing/iteration telemetry as JSON lines.\n";
 }
 
 Config parse_arguments(const std::vector<std::string>& argv) {
     Config c;
+    bool semantics_given = false;
     using Setter = std::function<void(const std::string&, const std::string&)>;
     std::map<std::string, Setter> valued = {
         {"--output_file", [&](const std::string& v, const std::string&) { c.output_file = v; }},
@@ -120,12 +127,13 @@ Config parse_arguments(const std::vector<std::string>& argv) {
         {"--batch_frames", [&](const std::string& v, const std::string& o) { c.batch_frames = to_int(v, o); }},
         {"--profile", [&](const std::string& v, const std::string&) { c.profile_file = v; }},
         {"--rtm_format", [&](const std::string& v, const std::string&) { c.rtm_format = v; }},
+        {"--fp64_semantics", [&](const std::string& v, const std::string&) { c.fp64_semantics = v; semantics_given = true; }},
     };
     std::map<std::string, bool*> flags = {
         {"--logarithmic", &c.logarithmic}, {"--no_guess", &c.no_guess},   {"--use_cpu", &c.use_cpu},
         {"--parallel_read", &c.parallel_read}, {"--resume", &c.resume}, {"--two_pass", &c.two_pass},
         {"--partition_voxels", &c.partition_voxels}, {"--rtm_bf16", &c.rtm_bf16},
-        {"--rtm_f16", &c.rtm_f16}, {"--rtm_f16_fused", &c.rtm_f16_fused},
+        {"--rtm_f16", &c.rtm_f16}, {"--rtm_f16_fused", &c.rtm_f16_fused}, {"--fp64", &c.fp64},
     };
     const std::map<std::string, std::string> alias = {
         {"-o", "--output_file"},           {"-t", "--time_range"},          {"-w", "--wavelength_threshold"},
@@ -195,6 +203,16 @@ Config parse_arguments(const std::vector<std::string>& argv) {
         throw Error("Argument rtm_format must be auto, dense or sparse, " + c.rtm_format + " given.");
     if (c.rtm_format == "sparse" && (c.partition_voxels || c.rtm_bf16 || c.rtm_f16 || (c.use_cpu && c.batch_frames > 1)))
         throw Error("Argument rtm_format sparse applies to fp32 pixel-row shards (and not to CPU batches).");
+    if (semantics_given && !c.fp64) throw Error("Argument fp64_semantics needs fp64.");
+    if (c.fp64_semantics != "gpu" && c.fp64_semantics != "cpu")
+        throw Error("Argument fp64_semantics must be gpu or cpu, " + c.fp64_semantics + " given.");
+    if (c.fp64 && c.use_cpu)
+        throw Error("Argument fp64 applies to the GPU solver: use_cpu already computes in double precision.");
+    if (c.fp64 && c.batch_frames > 1) throw Error("Argument fp64 applies to the single-frame GPU solver only.");
+    if (c.fp64 && c.partition_voxels) throw Error("Argument fp64 applies to pixel-row shards only (no partition_voxels).");
+    if (c.fp64 && (c.rtm_bf16 || c.rtm_f16))
+        throw Error("Argument fp64 applies to fp32 RTM storage only (no rtm_bf16 / rtm_f16).");
+    if (c.fp64 && c.rtm_format == "sparse") throw Error("Argument fp64 applies to dense shards only (no rtm_format sparse).");
     if (c.input_files.size() < 2)
         throw Error("At least two input file, one with RTM and one with image, are required, " +
                     std::to_string(c.input_files.size()) + " given.");

@@ -3,7 +3,7 @@
 // Same options, short aliases, defaults and validation as the reference CLI (reference
 // arguments.cpp:82-251, arguments.hpp:14-33), with an in-tree parser instead of p-ranav/argparse.
 // Extensions (not in the reference) are marked: --resume, --batch_frames, --two_pass, --partition_voxels,
-// --profile.
+// --profile, --fp64, --fp64_semantics.
 #pragma once
 
 #include <array>
@@ -42,6 +42,9 @@ struct Config {
     bool rtm_f16 = false;       // GPU: store the RTM shard as row-scaled f16 (exclusive with rtm_bf16)
     bool rtm_f16_fused = false; // GPU, with rtm_f16: run the fused single-pass f16 sweep (opt-in; else two-pass)
     bool rtm_bf16 = false;      // GPU: store the RTM shard in bf16 (fp32 products and sums)  // GPU: shard the RTM by voxel columns (all pixels per rank) instead of pixel rows
+    bool fp64 = false;          // GPU: solve in double precision (Engine64; fp32 dense pixel-row shards, frame by frame)
+    std::string fp64_semantics = "gpu";  // with fp64: "gpu" (the default GPU path's semantics in fp64) or "cpu"
+                                         // (what --use_cpu computes)
     std::string profile_file;   // JSON timing/telemetry sidecar
     bool help = false;
 };

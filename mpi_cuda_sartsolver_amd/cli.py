@@ -11,7 +11,8 @@ mpi_cuda_sartsolver_amd ...``: every rank's child reads RANK / WORLD_SIZE / LOCA
 MASTER_PORT) or by ``mpiexec`` (PMI_* / OMPI_* variables; the launcher's file descriptors stay open for the
 child, so PMI reaches it), like the reference's ``mpirun`` (reference main.cpp:63-68). The Python solver API
 (``models.sart.SARTSolver``, ``models.multiframe.MultiFrameSARTSolver``, ``models.cpu.CPUSARTSolver``) drives the
-same native engines for programmatic use.
+same native engines for programmatic use. ``--fp64 [--fp64_semantics gpu|cpu]`` solves on the GPU in double precision
+(``SARTSolver(..., precision="fp64")``): the answer the fp32 / bf16 / f16 paths are judged against.
 
 Signals: launchers stop their workers with SIGTERM (torchrun, mpiexec) or SIGINT / SIGHUP. This process forwards
 each of them to the driver and waits for it, so the driver never outlives its launcher holding a GPU or blocked

@@ -103,6 +103,12 @@ class SARTSolver:
 
     Thin wrapper of ``sart::Engine``: all device work, the per-iteration all-reduce (RCCL for the
     ``nccl`` process group, host TCP otherwise) and the convergence loop run in C++.
+
+    ``precision="fp64"`` builds ``sart::Engine64`` instead: every vector, product and sum in double precision over the
+    same fp32 dense row shard (two-pass fp64 kernels, csrc/kernels/projection64.hip), step for step what
+    ``CPUSARTSolver`` computes with the same ``semantics`` ("gpu": the default GPU path in fp64; "cpu": the reference
+    CPU solver). bf16 / f16 storage, sparse and column shards are refused. ``precision="fp32"`` (the default) builds
+    exactly the fp32 engine.
     """
 
     def __init__(self, rtm, laplacian: Optional[LaplacianCSR] = None,
@@ -111,7 +117,18 @@ class SARTSolver:
                  allow_zero_tolerance: bool = False, fused_variant: Optional[int] = None,
                  fused_rows_per_tile: Optional[int] = None, use_graph: Optional[bool] = None,
                  fused_min_bytes: float = 0.0, partition: Optional[str] = None, time_collectives: bool = False,
-                 f16_fused: bool = False):
+                 f16_fused: bool = False, precision: str = "fp32", semantics: str = "gpu"):
+        if precision not in ("fp32", "fp64"):
+            raise ValueError("precision must be 'fp32' or 'fp64'")
+        if semantics not in ("gpu", "cpu"):
+            raise ValueError("semantics must be 'gpu' or 'cpu'")
+        if precision == "fp32" and semantics != "gpu":
+            raise ValueError("semantics applies to precision='fp64' (the fp32 engine has the GPU semantics only)")
+        self.precision, self.semantics = precision, semantics
+        if precision == "fp64":  # the double-precision engine (sart::Engine64): fp32 dense row shards only
+            if use_fused:
+                raise ValueError("precision='fp64' runs the two-pass fp64 kernels (no fused sweep)")
+            use_fused = False
         self.k = hip()
         self.rtm = rtm
         self.dev = rtm.device
@@ -171,7 +188,14 @@ class SARTSolver:
             cfg.nvoxel_total = int(getattr(rtm, "nvoxel_total", rtm.nvoxel))
         device = self.dev.index if self.dev.index is not None else 0
         self.native_comm = native_communicator(self.comm, device)
-        if getattr(rtm, "nnz", None) is not None:  # SparseRTM: CSR / CSC kernels, two-pass sweep
+        if precision == "fp64":
+            # Engine64 refuses what it does not read (bf16 / f16 storage, sparse and column shards) with ValueError
+            is_sparse = getattr(rtm, "nnz", None) is not None
+            self.engine = self.k.Engine64(device, 0 if is_sparse else rtm.A.data_ptr(), rtm.npixel,
+                                          (rtm.npixel + 63) // 64 * 64 if is_sparse else rtm.nrows_pad, rtm.nvoxel,
+                                          (rtm.nvoxel + 63) // 64 * 64 if is_sparse else rtm.ld, self.native_comm, cfg,
+                                          gpu_semantics=semantics == "gpu", sparse=is_sparse)
+        elif getattr(rtm, "nnz", None) is not None:  # SparseRTM: CSR / CSC kernels, two-pass sweep
             if self.column_shard:
                 raise ValueError("a sparse RTM shard is a row shard")
             self.engine = self.k.Engine.from_sparse(device, *rtm.pointers(), rtm.nnz, rtm.npixel, rtm.nvoxel,
@@ -186,7 +210,7 @@ class SARTSolver:
 
     @property
     def use_fused(self) -> bool:
-        return self.engine.use_fused
+        return self.precision == "fp32" and self.engine.use_fused
 
     @property
     def shared_device(self) -> bool:
@@ -205,7 +229,7 @@ class SARTSolver:
 
     @property
     def geom(self):
-        return self.engine.geometry if self.engine.use_fused else None
+        return self.engine.geometry if self.use_fused else None
 
     @property
     def ray_density64(self) -> np.ndarray:

@@ -58,14 +58,29 @@ def _rel(a, b) -> float:
 def run(A: np.ndarray, G: np.ndarray, dev, *, iters: Iterable[int] = (1, 20), frames=(0, 1), beta: float = 1e-3,
         laplacian=None, batches=(32, 64, 128), variants=None, bf16: bool = True, column_shard: bool = True,
         sparse_A: Optional[np.ndarray] = None, emit: Callable[[Dict], None] = print, tag: str = "",
-        single: bool = True) -> List[Dict]:
-    """Every path x variant x iteration count; one record per (path, variant, iterations, frame)."""
+        single: bool = True, oracle: str = "torch") -> List[Dict]:
+    """Every path x variant x iteration count; one record per (path, variant, iterations, frame).
+    oracle: "torch" (models/oracle.py, the default) or "native": the double-precision engine (SARTSolver with
+    precision="fp64", gpu semantics, tolerance 0, fixed iterations) where it reads the shard (fp32 dense); bf16-stored
+    shards keep the torch loop, which dequantises them."""
     import torch
 
     from ..models.multiframe import MultiFrameSARTSolver
     from ..models.oracle import sart_oracle_f64
     from ..models.rtm import DenseRTM, SparseRTM
     from ..models.sart import SARTSolver, SolverParams
+
+    if oracle not in ("torch", "native"):
+        raise ValueError("oracle must be 'torch' or 'native'")
+    torch_oracle = sart_oracle_f64
+
+    def sart_oracle_f64(r, g, it, logarithmic=False, laplacian=None, beta_laplace=0.0):  # noqa: F811
+        if oracle == "native" and not r.is_16bit:
+            s = SARTSolver(r, laplacian, None, SolverParams(max_iterations=it, conv_tolerance=0.0,
+                                                            beta_laplace=beta_laplace if laplacian is not None else 1e-2),
+                           logarithmic=logarithmic, allow_zero_tolerance=True, precision="fp64", semantics="gpu")
+            return s.solve(g).solution
+        return torch_oracle(r, g, it, logarithmic=logarithmic, laplacian=laplacian, beta_laplace=beta_laplace)
 
     out: List[Dict] = []
     P, V = A.shape

@@ -32,6 +32,8 @@ def main():
     ap.add_argument("--variants", default="lin,lin+lap,log,log+lap")
     ap.add_argument("--frames", default="0,1")
     ap.add_argument("--no-single", action="store_true", help="multi-frame paths only (the two-pass yardstick stays)")
+    ap.add_argument("--oracle", default="torch", choices=("torch", "native"),
+                    help="the fp64 answer: the torch loop (models/oracle.py) or the double-precision engine (Engine64)")
     ap.add_argument("--tag", default="")
     ap.add_argument("--out", default=os.path.join(ROOT, "gpurun_out", "parity_at_scale.jsonl"))
     a = ap.parse_args()
@@ -72,7 +74,7 @@ def main():
         parity.run(A, G, dev, iters=iters, laplacian=L, bf16=not a.no_bf16, sparse_A=sparse_A, emit=emit,
                    batches=tuple(int(b) for b in a.batches.split(",") if b), variants=variants,
                    frames=tuple(int(f) for f in a.frames.split(",")), single=not a.no_single,
-                   column_shard=not a.no_single, tag=f"{A.shape[0]}x{A.shape[1]}{a.tag}")
+                   column_shard=not a.no_single, tag=f"{A.shape[0]}x{A.shape[1]}{a.tag}", oracle=a.oracle)
         del A, G, sparse_A
         torch.cuda.empty_cache()
     if a.wide or a.only_wide:
