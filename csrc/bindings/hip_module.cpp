@@ -868,6 +868,33 @@ PYBIND11_MODULE(_sart_hip, m) {
                                    P<const sart::SartState>(st), S(stream));
     }, py::arg("A"), py::arg("ld"), py::arg("nrows"), py::arg("w"), py::arg("nsplit"), py::arg("partial"),
        py::arg("st") = 0, py::arg("stream") = 0);
+    // fit64.hip: F [nv][ldf] = A X^T for nv <= 8 fp64 vectors X [nv][ldx] per pass over the shard (a
+    // row or a column shard in its storage; rscale: an f16 shard's [nrows_pad] scales, then their inverses)
+    m.def("fit64_group", &sart::fit64_group, py::arg("bf16") = false, py::arg("f16") = false,
+          py::arg("sparse") = false);
+    m.def("fit_forward", [](uintptr_t A, int64_t ld, int64_t nrows, int64_t nrows_pad, int64_t nvoxel, uintptr_t X,
+                            int64_t ldx, int nv, uintptr_t F, int64_t ldf, uintptr_t stream, bool bf16, bool f16,
+                            uintptr_t rscale) {
+        sart::launch_fit64(P<const void>(A), bf16, f16, P<const float>(rscale), ld, nrows, nrows_pad, nvoxel,
+                           P<const double>(X), ldx, nv, P<double>(F), ldf, S(stream));
+    }, py::arg("A"), py::arg("ld"), py::arg("nrows"), py::arg("nrows_pad"), py::arg("nvoxel"), py::arg("X"),
+       py::arg("ldx"), py::arg("nv"), py::arg("F"), py::arg("ldf"), py::arg("stream") = 0, py::arg("bf16") = false,
+       py::arg("f16") = false, py::arg("rscale") = 0);
+    // sparse shard: the CSR arrays; Xt: ld x 8 doubles of scratch; lanes: lanes per row (0: a fixed 8)
+    m.def("fit_forward_csr", [](uintptr_t row_ptr, uintptr_t col, uintptr_t val, int64_t nnz, int64_t nrows,
+                                int64_t nvoxel, int64_t ld, uintptr_t X, int64_t ldx, int nv, uintptr_t Xt,
+                                uintptr_t F, int64_t ldf, uintptr_t stream, int lanes) {
+        sart::SparseRtm s;
+        s.row_ptr = P<const int64_t>(row_ptr);
+        s.col = P<const int32_t>(col);
+        s.val = P<const float>(val);
+        s.nnz = nnz;
+        s.lanes_rows = lanes;
+        sart::launch_fit64_csr(s, nrows, nvoxel, ld, P<const double>(X), ldx, nv, P<double>(Xt), P<double>(F), ldf,
+                               S(stream));
+    }, py::arg("row_ptr"), py::arg("col"), py::arg("val"), py::arg("nnz"), py::arg("nrows"), py::arg("nvoxel"),
+       py::arg("ld"), py::arg("X"), py::arg("ldx"), py::arg("nv"), py::arg("Xt"), py::arg("F"), py::arg("ldf"),
+       py::arg("stream") = 0, py::arg("lanes") = 0);
     m.def("prep_rows", [](uintptr_t g, int64_t nrows, int64_t nrows_pad, double inv_s, uintptr_t ray_length,
                           float len_thres, uintptr_t ghat, uintptr_t arow, uintptr_t gpos, uintptr_t wo,
                           uintptr_t stream) {

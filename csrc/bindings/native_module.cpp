@@ -11,6 +11,7 @@
 #include "cpu_solver.hpp"
 #include "sparse_csr.hpp"
 #include "host_comm.hpp"
+#include "fit.hpp"
 #include "fixtures.hpp"
 #include "frames.hpp"
 #include "h5.hpp"
@@ -78,6 +79,8 @@ PYBIND11_MODULE(_sart_native, m) {
         .def_readwrite("rtm_format", &Config::rtm_format)
         .def_readwrite("fp64", &Config::fp64)
         .def_readwrite("fp64_semantics", &Config::fp64_semantics)
+        .def_readwrite("fit", &Config::fit)
+        .def_readwrite("fit_only", &Config::fit_only)
         .def_readwrite("profile_file", &Config::profile_file)
         .def_readwrite("help", &Config::help);
     m.def("parse_arguments", &parse_arguments, py::arg("argv"));
@@ -315,6 +318,62 @@ PYBIND11_MODULE(_sart_native, m) {
         }
         return out;
     });
+
+    // fit diagnostics (fit.hpp): F [nv, P] = A X^T in fp64 for X [nv, >= V]; dense fp32 rows or CSR arrays
+    m.def("cpu_fit_forward", [](py::array_t<float, py::array::c_style> A, int64_t P, int64_t V, f64arr X) {
+        auto bi = A.request();
+        check_rows(bi, P, V, bi.ndim == 2 ? bi.shape[1] : 0);
+        if (X.ndim() != 2 || X.shape(1) < V) throw std::invalid_argument("X must be [nv, >= V]");
+        const int nv = (int)X.shape(0);
+        py::array_t<double> F({(py::ssize_t)nv, (py::ssize_t)P});
+        const float* a = static_cast<const float*>(bi.ptr);
+        const double* xp = X.data();
+        double* fp = F.mutable_data();
+        const int64_t ld = bi.shape[1], ldx = X.shape(1);
+        {
+            py::gil_scoped_release nogil;
+            cpu_fit_forward(a, P, V, ld, xp, ldx, nv, fp, P);
+        }
+        return F;
+    }, py::arg("A"), py::arg("P"), py::arg("V"), py::arg("X"));
+    m.def("cpu_fit_forward_csr", [](int64_t nrows, int64_t ncols,
+                                    py::array_t<int64_t, py::array::c_style | py::array::forcecast> ptr,
+                                    py::array_t<int32_t, py::array::c_style | py::array::forcecast> idx,
+                                    py::array_t<float, py::array::c_style | py::array::forcecast> val, f64arr X) {
+        sart::HostCsr a;
+        a.nrows = nrows;
+        a.ncols = ncols;
+        a.ptr.assign(ptr.data(), ptr.data() + ptr.size());
+        a.idx.assign(idx.data(), idx.data() + idx.size());
+        a.val.assign(val.data(), val.data() + val.size());
+        if (X.ndim() != 2 || X.shape(1) < ncols) throw py::value_error("X must be [nv, >= ncols]");
+        const int nv = (int)X.shape(0);
+        py::array_t<double> F({(py::ssize_t)nv, (py::ssize_t)nrows});
+        try {
+            cpu_fit_forward(a, X.data(), X.shape(1), nv, F.mutable_data(), nrows);
+        } catch (const std::invalid_argument& e) {
+            throw py::value_error(e.what());
+        }
+        return F;
+    }, py::arg("nrows"), py::arg("ncols"), py::arg("ptr"), py::arg("idx"), py::arg("val"), py::arg("X"));
+    m.def("fit_statistics", [](f64arr f, f64arr g, f64arr ell, double threshold, const std::vector<int64_t>& camera_pixels) {
+        if (f.size() != g.size() || ell.size() != g.size()) throw py::value_error("f, g and ell must have one length");
+        FitStats s;
+        try {
+            s = fit_statistics(f.data(), g.data(), ell.data(), (int64_t)g.size(), threshold, camera_pixels);
+        } catch (const std::invalid_argument& e) {
+            throw py::value_error(e.what());
+        }
+        py::dict d;
+        d["residual_norm"] = s.residual_norm;
+        d["measurement_norm"] = s.measurement_norm;
+        d["residual_max"] = s.residual_max;
+        d["pixels"] = s.pixels;
+        d["residual_norm_camera"] = arr(s.residual_norm_camera);
+        d["measurement_norm_camera"] = arr(s.measurement_norm_camera);
+        d["pixels_camera"] = arr(s.pixels_camera);
+        return d;
+    }, py::arg("f"), py::arg("g"), py::arg("ell"), py::arg("threshold"), py::arg("camera_pixels"));
 
     // host CSR of (row, col, value) entries (later duplicates win, zeros dropped) and its transpose (= CSC)
     m.def("csr_from_entries", [](int64_t nrows, int64_t ncols, py::array_t<int64_t, py::array::c_style | py::array::forcecast> r,

@@ -16,7 +16,8 @@
 //     collective (the reference calls std::exit on one rank).
 // Extensions: --resume, --two_pass, --profile FILE (JSON lines per frame: iterations, convergence, it/s,
 // GFLOPS, RTM GB/s, GPU time in the all-reduces, communicators), --batch_frames N (N
-// frames solved together by the multi-frame MFMA engine; batches warm-start from the previous batch).
+// frames solved together by the multi-frame MFMA engine; batches warm-start from the previous batch), --fit / --fit_only
+// (after the frames: fp64 fitted images and residuals of every stored solution into the output's /fit group).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -32,6 +33,7 @@
 #include <memory>
 #include <mutex>
 #include <condition_variable>
+#include <sstream>
 #include <stdexcept>
 #include <string>
 #include <sys/prctl.h>
@@ -51,6 +53,7 @@
 #include "../kernels/launchers.hpp"
 #include "../native/config.hpp"
 #include "../native/cpu_solver.hpp"
+#include "../native/fit.hpp"
 #include "../native/frames.hpp"
 #include "../native/h5.hpp"
 #include "../native/host_comm.hpp"
@@ -370,6 +373,146 @@ std::string json_escape(const std::string& s) {
     return o;
 }
 
+// What the fit pass projects with: exactly one of the four shards
+struct FitShard {
+    const DeviceShard* dense = nullptr;         // GPU, dense storage (row or column shard)
+    const DeviceSparseShard* sparse = nullptr;  // GPU, CSR
+    const float* host = nullptr;                // --use_cpu, dense fp32 [rows][nvoxel]
+    const HostCsr* csr = nullptr;               // --use_cpu, CSR
+};
+
+// --fit / --fit_only: the fitted images f = A x (fp64) of every solution stored in the output file, in groups of up to
+// 8 per pass over the shard (4 on bf16 / f16 shards; SART_FIT_GROUP overrides), and their residuals against the
+// measured composite frames, into the file's /fit group (docs/FORMATS.md). Main thread, after the frame loop, with the solution writer closed. Rank 0 reads the stored
+// solutions and broadcasts them, every rank projects on its shard (row shards: its rows; column shards: partial sums
+// over its voxels for all pixels), the images are summed over the ranks through a zero-filled host all-reduce, rank 0
+// computes the statistics and writes. A value depends on its pixel row and solution only (csrc/kernels/fit64.hip), so
+// the file is the same for any grouping and any number of row-shard ranks.
+void run_fit_pass(const Config& cfg, const InputSet& in, const std::vector<std::array<double, 4>>& intervals,
+                  HostComm* host, const FitShard& sh, const Block& blk, const Block& vblk, const CompositeImage& image,
+                  std::ofstream& profile, const std::string& storage) {
+    const int rank = host->rank(), size = host->size();
+    const auto t_fit = std::chrono::steady_clock::now();
+    const uint64_t npixel = in.npixel, nvoxel = in.nvoxel;
+    std::vector<double> times;
+    if (rank == 0) times = read_solution_times(cfg.output_file);
+    uint64_t T = times.size();
+    host->broadcast_host(&T, sizeof(T), 0);
+    if (T == 0)
+        throw Error("Argument " + std::string(cfg.fit_only ? "fit_only" : "fit") + " needs solutions to project: " +
+                    cfg.output_file + " is missing or holds none.");
+    times.resize(T);
+    host->broadcast_host(times.data(), T * sizeof(double), 0);
+    // a stored frame belongs to the composite frame of its time (the rule of --resume)
+    std::vector<uint64_t> frame_of(T);
+    for (uint64_t k = 0; k < T; ++k) {
+        uint64_t i = 0;
+        while (i < image.nframe() && !(std::abs(image.frame_time(i) - times[k]) <= 1e-12)) ++i;
+        if (i == image.nframe()) {
+            std::ostringstream os;
+            os.precision(17);
+            os << "Stored solution time " << times[k] << " has no composite frame in the selected time range.";
+            throw Error(os.str());
+        }
+        frame_of[k] = i;
+    }
+    const bool gpu = sh.dense || sh.sparse;
+    // solutions per pass over the shard: the width at which a frame costs least for the storage (8; 4 on 16-bit shards)
+    int group = fit64_group(sh.dense && sh.dense->bf16, sh.dense && sh.dense->f16, !sh.dense);
+    if (const char* e = std::getenv("SART_FIT_GROUP"); e && *e) {  // (an A/B knob: the file does not depend on it)
+        group = std::atoi(e);
+        if (group < 1 || group > 8) throw Error(std::string("SART_FIT_GROUP must be within 1 .. 8, not '") + e + "'");
+    }
+    // device operands: X [group][ldx], F [group][ldf], the sparse kernel's voxel-major copy of X
+    DeviceArray<double> dX, dF, dXt;
+    int64_t ldx = 0, ldf = 0;
+    SparseRtm view;
+    if (sh.dense) {
+        ldx = sh.dense->ld;
+        ldf = sh.dense->nrows_pad;
+    } else if (sh.sparse) {
+        ldx = (sh.sparse->nvoxel + 63) / 64 * 64;
+        ldf = (sh.sparse->nrows + 63) / 64 * 64;
+        dXt.resize((size_t)ldx * 8);
+        view = sh.sparse->view();
+    }
+    if (gpu) {
+        dX.resize((size_t)group * ldx);
+        dF.resize((size_t)group * ldf);
+    }
+    // out [n][npixel] += this rank's part of A X^T for X [n][nvoxel] (out zero-filled by the caller)
+    auto project = [&](const double* X, int n, double* out) {
+        if (gpu) {
+            for (int j = 0; j < n; ++j)
+                hip_ok(hipMemcpy(dX.get() + (size_t)j * ldx, X + (size_t)j * nvoxel + vblk.offset,
+                                 vblk.size * sizeof(double), hipMemcpyHostToDevice), "H2D fit solutions");
+            if (sh.dense)
+                launch_fit64(sh.dense->A, sh.dense->bf16, sh.dense->f16, sh.dense->rsc.get(), sh.dense->ld,
+                             sh.dense->nrows, sh.dense->nrows_pad, sh.dense->nvoxel, dX.get(), ldx, n, dF.get(), ldf,
+                             nullptr);
+            else
+                launch_fit64_csr(view, sh.sparse->nrows, sh.sparse->nvoxel, ldx, dX.get(), ldx, n, dXt.get(), dF.get(),
+                                 ldf, nullptr);
+            for (int j = 0; j < n; ++j)
+                hip_ok(hipMemcpy(out + (size_t)j * npixel + blk.offset, dF.get() + (size_t)j * ldf,
+                                 blk.size * sizeof(double), hipMemcpyDeviceToHost), "D2H fitted images");
+        } else if (sh.csr) {
+            cpu_fit_forward(*sh.csr, X, (int64_t)nvoxel, n, out + blk.offset, (int64_t)npixel);
+        } else {
+            cpu_fit_forward(sh.host, (int64_t)blk.size, (int64_t)nvoxel, (int64_t)nvoxel, X, (int64_t)nvoxel, n,
+                            out + blk.offset, (int64_t)npixel);
+        }
+    };
+    // the ray lengths: the fit projection of the all-ones vector (one extra pass; any storage, no engine needed)
+    std::vector<double> ell(npixel, 0.0);
+    {
+        const std::vector<double> ones(nvoxel, 1.0);
+        project(ones.data(), 1, ell.data());
+        host->all_reduce_host(ell.data(), ell.size(), ReduceOp::kSum);
+    }
+    std::unique_ptr<FitWriter> fw;
+    std::unique_ptr<CompositeImage> full;  // rank 0: the measured frames over all pixels
+    std::vector<int64_t> camera_pixels;
+    if (rank == 0) {
+        for (const auto& cam : in.camera_names) {
+            const auto& mask = in.frame_masks.at(cam);
+            camera_pixels.push_back((int64_t)std::count_if(mask.begin(), mask.end(), [](int32_t v) { return v != 0; }));
+        }
+        full = std::make_unique<CompositeImage>(in.image_files, in.frame_masks, intervals, npixel, 0);
+        full->set_max_cache_size((uint64_t)cfg.max_cached_frames);
+        fw = std::make_unique<FitWriter>(cfg.output_file, T, npixel, in.camera_names.size());
+    }
+    std::vector<double> X((size_t)group * nvoxel), F((size_t)group * npixel);
+    uint64_t groups = 0;
+    for (uint64_t k0 = 0; k0 < T; k0 += group, ++groups) {
+        const int n = (int)std::min<uint64_t>(group, T - k0);
+        if (rank == 0) {
+            const std::vector<double> rows = read_solution_rows(cfg.output_file, k0, n, nvoxel);
+            std::copy(rows.begin(), rows.end(), X.begin());
+        }
+        host->broadcast_host(X.data(), (size_t)n * nvoxel * sizeof(double), 0);
+        std::fill(F.begin(), F.begin() + (size_t)n * npixel, 0.0);
+        project(X.data(), n, F.data());
+        host->all_reduce_host(F.data(), (size_t)n * npixel, ReduceOp::kSum);
+        if (rank == 0)
+            for (int j = 0; j < n; ++j) {
+                const std::vector<double> g = full->frame(frame_of[k0 + j]);
+                const double* f = F.data() + (size_t)j * npixel;
+                fw->write(k0 + j, f, fit_statistics(f, g.data(), ell.data(), (int64_t)npixel,
+                                                    cfg.ray_length_threshold, camera_pixels));
+            }
+    }
+    host->barrier();
+    if (rank == 0) {
+        const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_fit).count();
+        std::cout << "Fit of " << T << " frame(s) in: " << ms << " ms" << std::endl;
+        if (profile.is_open())
+            profile << "{\"fit\": true, \"frames\": " << T << ", \"groups\": " << groups << ", \"fit_ms\": " << ms
+                    << ", \"rtm_storage\": \"" << storage << "\", \"rtm_format\": \""
+                    << ((sh.sparse || sh.csr) ? "sparse" : "dense") << "\", \"ranks\": " << size << "}\n";
+    }
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -544,6 +687,7 @@ int main(int argc, char** argv) {
         std::unique_ptr<MultiFrameEngine> mf;
         std::unique_ptr<CpuSolver> cpu;
         const bool batched = gpu && cfg.batch_frames > 1;
+        const bool solve = !cfg.fit_only;  // --fit_only: the shard alone, for the fit pass
         if (batched) {
             EngineConfig ec;
             static_cast<SolverParams&>(ec) = params;
@@ -572,9 +716,9 @@ int main(int argc, char** argv) {
             engine64 = std::make_unique<Engine64>(device, dshard->A, dshard->nrows, dshard->nrows_pad, dshard->nvoxel,
                                                   dshard->ld, dcomm.get(), ec, cfg.fp64_semantics == "gpu");
             if (lap.nnz()) engine64->set_laplacian(lap.row_ptr.data(), lap.col.data(), lap.val.data(), lap.nnz());
-        } else if (gpu) {
+        } else if (gpu && solve) {
             engine = make_engine(1.0);
-        } else {
+        } else if (solve) {
             if (sparse)
                 cpu = std::make_unique<CpuSolver>(std::move(hcsr), host, params, false);
             else
@@ -589,7 +733,7 @@ int main(int argc, char** argv) {
         double skip_until = -std::numeric_limits<double>::infinity();
         std::vector<double> warm;
         bool appended = false;
-        if (rank == 0) {
+        if (rank == 0 && solve) {
             if (cfg.resume && file_exists(cfg.output_file)) {
                 const StoredSolutions st = read_solution_file(cfg.output_file);
                 if (!st.time.empty()) {
@@ -625,7 +769,7 @@ int main(int argc, char** argv) {
             double fl[2] = {(double)lstats.f16_flushed, (double)lstats.f16_nonzeros};
             host->all_reduce_host(fl, 2, ReduceOp::kSum);
             const std::string storage = !gpu || sparse ? "fp32" : (cfg.rtm_f16 ? "f16" : (cfg.rtm_bf16 ? "bf16" : "fp32"));
-            std::string path = "cpu";
+            std::string path = solve ? "cpu" : "none (fit only)";
             if (mf)
                 path = "multi-frame " + mf->forward_split() + " / " + mf->backproject_split();
             else if (engine64)
@@ -664,7 +808,7 @@ int main(int argc, char** argv) {
 
         std::vector<uint64_t> frames;
         for (uint64_t i = 0; i < image.nframe(); ++i)
-            if (image.frame_time(i) > skip_until + 1e-12) frames.push_back(i);
+            if (solve && image.frame_time(i) > skip_until + 1e-12) frames.push_back(i);
         const size_t nframes_total = frames.size();
         const auto t_loop = std::chrono::steady_clock::now();
         if (batched) {
@@ -927,7 +1071,7 @@ int main(int argc, char** argv) {
                 (info.nonfinite && !std::all_of(x.begin(), x.end(), [](double v) { return std::isfinite(v); })))
                 solution.clear();
         }
-        if (rank == 0) {
+        if (rank == 0 && solve) {
             writer->flush();
             if (!appended) voxelgrid.write(cfg.output_file, "voxel_map");
             // the whole frame loop (reads not hidden by the prefetch, solves, output, the final flush)
@@ -938,6 +1082,25 @@ int main(int argc, char** argv) {
             }
         }
         host->barrier();
+        if (cfg.fit || cfg.fit_only) {
+            writer.reset();  // flushed above: the file is closed before the /fit group is added to it
+            engine.reset(), lead_engine.reset(), engine64.reset(), mf.reset();
+            if (!gpu && sparse && cpu) {  // the CPU solver took the CSR rows: read them again
+                cpu.reset();
+                hcsr = RtmReader(in.rtm_files, in.rtm_name, in.nvoxel).read_csr(blk.offset, blk.offset + blk.size);
+            }
+            FitShard fs;
+            if (gpu && sparse)
+                fs.sparse = sshard.get();
+            else if (gpu)
+                fs.dense = dshard.get();
+            else if (sparse)
+                fs.csr = &hcsr;
+            else
+                fs.host = hshard.data();
+            const std::string storage = !gpu || sparse ? "fp32" : (cfg.rtm_f16 ? "f16" : (cfg.rtm_bf16 ? "bf16" : "fp32"));
+            run_fit_pass(cfg, in, intervals, host, fs, blk, vblk, image, profile, storage);
+        }
     } catch (const std::exception& e) {
         std::cerr << "rank " << rank << ": " << e.what() << std::endl;
         if (dcomm) dcomm->abort();

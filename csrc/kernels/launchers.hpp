@@ -128,6 +128,21 @@ void launch_decide64(SartState* st, const double* Fslot, hipStream_t stream);
 void launch_update64(bool logmode, double* x, const double* red, const double* O, const double* pen,
                      const int32_t* valid, const double* rho_s, double alpha, double eps, bool gpu_semantics, int64_t n,
                      const SartState* st, hipStream_t stream);
+// fit64.hip: fit projections F[j][p] = sum_v A[p][v] X[j][v] for nv <= 8 fp64 vectors per pass over
+// the shard (fp64 FMAs; no atomics; F[j][p] depends on row p and vector j only, not on nv, the slot or the grid).
+// X: [nv][ldx] (ldx >= ld, even; entries at and beyond nvoxel are not used), F: [nv][ldf] (ldf >= nrows; rows beyond
+// nrows are neither read nor written). A shape without a kernel throws by name before any launch.
+// vectors per pass at which a frame costs least for the storage (measured: 8, and 4 on bf16 / f16 shards)
+int fit64_group(bool bf16, bool f16, bool sparse);
+// dense shard [nrows_pad][ld] in the storage the engines select: fp32, bf16 bits (bf16) or row-scaled f16 bits (f16,
+// row_scale: the shard's [nrows_pad] scales, then their inverses)
+void launch_fit64(const void* A, bool bf16, bool f16, const float* row_scale, int64_t ld, int64_t nrows,
+                  int64_t nrows_pad, int64_t nvoxel, const double* X, int64_t ldx, int nv, double* F, int64_t ldf,
+                  hipStream_t stream);
+// sparse shard (the CSR arrays of s; lanes per row: s.lanes_rows, or a fixed 8 when it is 0 -- never derived from the
+// shard, so a row's bits do not depend on the row partition); Xt: scratch of ld x 8 doubles (X voxel-major, written here)
+void launch_fit64_csr(const SparseRtm& s, int64_t nrows, int64_t nvoxel, int64_t ld, const double* X, int64_t ldx,
+                      int nv, double* Xt, double* F, int64_t ldf, hipStream_t stream);
 // sart_update.hip
 void launch_prep_rows(const double* g, int64_t nrows, int64_t nrows_pad, double inv_s, const float* ray_length,
                       float len_thres, float* ghat, float* arow, float* gpos, float* wo, hipStream_t stream);

@@ -103,6 +103,14 @@ std::string usage() {
            "  --fp64_semantics S          gpu | cpu, with --fp64. gpu: the default GPU path (normalisation,\n"
            "                              epsilon 1e-7, fp32-rounded thresholds) evaluated in fp64; cpu: what\n"
            "                              --use_cpu computes. [default: gpu]\n"
+           "  --fit                       After the frames, project every solution in the output file back through the\n"
+           "                              RTM as stored (f = A x in fp64; up to 8 solutions per pass over the matrix,\n"
+           "                              4 on bf16 / f16 shards) and write the fitted images and the residuals\n"
+           "                              against the measured frames, in all and per camera, into the output\n"
+           "                              file's /fit group.\n"
+           "  --fit_only                  Solve nothing: load the RTM as the other options say and run the fit pass\n"
+           "                              over the solutions already in the output file (e.g. an --rtm_bf16 solution\n"
+           "                              against the fp32 matrix). Not with --resume, --batch_frames > 1 or --fp64.\n"
            "  --profile FILE              Write per-frame timing/iteration telemetry as JSON lines.\n";
 }
 
@@ -134,6 +142,7 @@ Config parse_arguments(const std::vector<std::string>& argv) {
         {"--parallel_read", &c.parallel_read}, {"--resume", &c.resume}, {"--two_pass", &c.two_pass},
         {"--partition_voxels", &c.partition_voxels}, {"--rtm_bf16", &c.rtm_bf16},
         {"--rtm_f16", &c.rtm_f16}, {"--rtm_f16_fused", &c.rtm_f16_fused}, {"--fp64", &c.fp64},
+        {"--fit", &c.fit}, {"--fit_only", &c.fit_only},
     };
     const std::map<std::string, std::string> alias = {
         {"-o", "--output_file"},           {"-t", "--time_range"},          {"-w", "--wavelength_threshold"},
@@ -213,6 +222,10 @@ Config parse_arguments(const std::vector<std::string>& argv) {
     if (c.fp64 && (c.rtm_bf16 || c.rtm_f16))
         throw Error("Argument fp64 applies to fp32 RTM storage only (no rtm_bf16 / rtm_f16).");
     if (c.fp64 && c.rtm_format == "sparse") throw Error("Argument fp64 applies to dense shards only (no rtm_format sparse).");
+    if (c.fit_only && c.resume) throw Error("Argument fit_only solves no frame: it cannot be combined with resume.");
+    if (c.fit_only && c.batch_frames > 1)
+        throw Error("Argument fit_only solves no frame: it cannot be combined with batch_frames > 1.");
+    if (c.fit_only && c.fp64) throw Error("Argument fit_only solves no frame: it cannot be combined with fp64.");
     if (c.input_files.size() < 2)
         throw Error("At least two input file, one with RTM and one with image, are required, " +
                     std::to_string(c.input_files.size()) + " given.");

@@ -3,7 +3,7 @@
 // Same options, short aliases, defaults and validation as the reference CLI (reference
 // arguments.cpp:82-251, arguments.hpp:14-33), with an in-tree parser instead of p-ranav/argparse.
 // Extensions (not in the reference) are marked: --resume, --batch_frames, --two_pass, --partition_voxels,
-// --profile, --fp64, --fp64_semantics.
+// --profile, --fp64, --fp64_semantics, --fit, --fit_only.
 #pragma once
 
 #include <array>
@@ -45,6 +45,8 @@ struct Config {
     bool fp64 = false;          // GPU: solve in double precision (Engine64; fp32 dense pixel-row shards, frame by frame)
     std::string fp64_semantics = "gpu";  // with fp64: "gpu" (the default GPU path's semantics in fp64) or "cpu"
                                          // (what --use_cpu computes)
+    bool fit = false;           // after the frames: fp64 fitted images f = A x and residuals into the output's /fit group
+    bool fit_only = false;      // no solve: the fit pass alone over the solutions already in the output file
     std::string profile_file;   // JSON timing/telemetry sidecar
     bool help = false;
 };

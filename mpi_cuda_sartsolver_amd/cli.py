@@ -12,7 +12,10 @@ MASTER_PORT) or by ``mpiexec`` (PMI_* / OMPI_* variables; the launcher's file de
 child, so PMI reaches it), like the reference's ``mpirun`` (reference main.cpp:63-68). The Python solver API
 (``models.sart.SARTSolver``, ``models.multiframe.MultiFrameSARTSolver``, ``models.cpu.CPUSARTSolver``) drives the
 same native engines for programmatic use. ``--fp64 [--fp64_semantics gpu|cpu]`` solves on the GPU in double precision
-(``SARTSolver(..., precision="fp64")``): the answer the fp32 / bf16 / f16 paths are judged against.
+(``SARTSolver(..., precision="fp64")``): the answer the fp32 / bf16 / f16 paths are judged against. ``--fit`` adds, after
+the frames, the fp64 fitted images ``f = A x`` of every stored solution through the matrix as stored and their
+residuals against the measured frames (the output file's ``/fit`` group, docs/FORMATS.md); ``--fit_only`` runs that
+pass alone over an existing output file (``SARTSolver.fit`` / ``models.fit.fit_forward`` in Python).
 
 Signals: launchers stop their workers with SIGTERM (torchrun, mpiexec) or SIGINT / SIGHUP. This process forwards
 each of them to the driver and waits for it, so the driver never outlives its launcher holding a GPU or blocked

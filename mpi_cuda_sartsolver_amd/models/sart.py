@@ -270,3 +270,20 @@ class SARTSolver:
     def forward_project(self, x_local) -> np.ndarray:
         """f = A x for this shard (utility / tests)."""
         return self.engine.forward(_host_f64(x_local))
+
+    def fit(self, measurement, solution, camera_pixels=None):
+        """How well ``solution`` explains ``measurement``: the fp64 fitted image f = A x of this shard's pixels through
+        the matrix as stored (models/fit.py, csrc/kernels/fit64.hip) and the residual statistics over the pixels the
+        solver uses (measurement >= 0, ray length above the threshold; ray lengths: ``ray_length64``). ``solution``:
+        this shard's voxels; a column shard's partial images are summed over ``self.comm`` (``measurement``: all
+        pixels). Returns a ``FitResult``; ``camera_pixels`` splits the statistics by camera."""
+        from .fit import fit_forward, fit_statistics
+
+        g = _host_f64(measurement)
+        f = fit_forward(self.rtm, _host_f64(solution))
+        if self.column_shard:
+            t = torch.from_numpy(f)
+            if getattr(self.comm, "backend", None) == "nccl":
+                t = t.to(self.dev)
+            f = self.comm.all_reduce_(t).cpu().numpy()
+        return fit_statistics(f, g, self.ray_length64, self.params.ray_length_threshold, camera_pixels)
