@@ -185,17 +185,19 @@ def build_driver(verbose: bool = True) -> Path:
     objdir = BUILDDIR / "driver"
     objdir.mkdir(parents=True, exist_ok=True)
     headers = (sorted((CSRC / "kernels").glob("*.hpp")) + sorted((CSRC / "engine").glob("*.hpp")) +
-               sorted((CSRC / "native").glob("*.hpp")))
-    src = CSRC / "driver" / "sartsolver_main.cpp"
+               sorted((CSRC / "native").glob("*.hpp")) + sorted((CSRC / "driver").glob("*.hpp")))
     dflags = ["-O2", "-std=c++17", "-Wall", "-D__HIP_PLATFORM_AMD__", "-DSART_HAVE_HDF5=1",
               f"-isystem{HDF5_PREFIX / 'include'}", f"-I{ROCM / 'include'}"]
-    dobj = objdir / "sartsolver_main.o"
-    _compile_many([([hipcc, *dflags, "-c", str(src), "-o", str(dobj)], dobj, _digest([src, *headers], dflags))],
-                  verbose)
+    jobs, dobjs = [], []
+    for src in sorted((CSRC / "driver").glob("*.cpp")):
+        obj = objdir / (src.stem + ".o")
+        jobs.append(([hipcc, *dflags, "-c", str(src), "-o", str(obj)], obj, _digest([src, *headers], dflags)))
+        dobjs.append(obj)
+    _compile_many(jobs, verbose)
     hip_objs = [o for o in sorted((BUILDDIR / "hip").glob("*.o")) if o.name != "hip_module.o"]
     native_objs = [o for o in sorted((BUILDDIR / "native").glob("*.o"))
                    if o.name not in ("native_module.o", "host_comm.o", "host_comm_mpi.o", "solver_params.o")]
-    objs = [dobj, *hip_objs, *native_objs]
+    objs = [*dobjs, *hip_objs, *native_objs]
     libdir = LIBDIR / "hdf5"  # private RUNPATH entry: only libhdf5
     libdir.mkdir(parents=True, exist_ok=True)
     for so in HDF5_PREFIX.joinpath("lib").glob("libhdf5.so.*"):
