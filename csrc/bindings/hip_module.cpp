@@ -265,6 +265,7 @@ static void bind_engine(py::module_& m) {
         .def_readwrite("check_interval", &sart::EngineConfig::check_interval)
         .def_readwrite("use_fused", &sart::EngineConfig::use_fused)
         .def_readwrite("mf_frames", &sart::EngineConfig::mf_frames)
+        .def_readwrite("mf_frame_beta", &sart::EngineConfig::mf_frame_beta)
         .def_readwrite("fused_min_bytes", &sart::EngineConfig::fused_min_bytes)
         .def_readwrite("column_shard", &sart::EngineConfig::column_shard)
         .def_readwrite("col_offset", &sart::EngineConfig::col_offset)
@@ -477,7 +478,8 @@ static void bind_engine(py::module_& m) {
                 py::array_t<float, py::array::c_style | py::array::forcecast> val) {
                  e.set_laplacian(rp.data(), col.data(), val.data(), (int64_t)val.size());
              })
-        .def("solve_batch", [](sart::MultiFrameEngine& e, f64arr g, py::object x0, bool chain, bool record_starts) -> py::tuple {
+        .def("solve_batch", [](sart::MultiFrameEngine& e, f64arr g, py::object x0, bool chain, bool record_starts,
+                               py::object betas) -> py::tuple {
             if (g.ndim() != 2 || g.shape(1) != e.nrows())
                 throw py::value_error("measurements must be [nframes, nrows of the local shard]");
             const int nf = (int)g.shape(0);
@@ -488,21 +490,32 @@ static void bind_engine(py::module_& m) {
                 if ((int64_t)x0a.size() != e.nvoxel()) throw py::value_error("x0 must have nvoxel elements");
                 x0p = x0a.data();
             }
+            // betas (optional): a Laplacian weight per frame, nframes entries (fp32 on the device, as beta_laplace)
+            py::array_t<float, py::array::c_style | py::array::forcecast> ba;
+            const float* bp = nullptr;
+            if (!betas.is_none()) {
+                ba = betas.cast<py::array_t<float, py::array::c_style | py::array::forcecast>>();
+                if ((int64_t)ba.size() != nf) throw py::value_error("betas must have one entry per frame");
+                bp = ba.data();
+            }
             py::array_t<double> x({(py::ssize_t)nf, (py::ssize_t)e.nvoxel()});
             py::array_t<double> st({(py::ssize_t)(record_starts ? nf : 0), (py::ssize_t)e.nvoxel()});
             double* xp = x.mutable_data();
             double* sp = record_starts ? st.mutable_data() : nullptr;
             const double* gp = g.data();
             std::vector<sart::SolveInfo> infos;
-            {
+            try {
                 py::gil_scoped_release rel;
-                infos = e.solve_batch(gp, nf, xp, x0p, chain, sp);
+                infos = e.solve_batch(gp, nf, xp, x0p, chain, sp, bp);
+            } catch (const std::invalid_argument& ex) {
+                throw py::value_error(ex.what());
             }
             py::list li;
             for (const auto& i : infos) li.append(solve_info(i));
             if (record_starts) return py::make_tuple(x, li, st);
             return py::make_tuple(x, li);
-        }, py::arg("g"), py::arg("x0") = py::none(), py::arg("chain") = false, py::arg("record_starts") = false)
+        }, py::arg("g"), py::arg("x0") = py::none(), py::arg("chain") = false, py::arg("record_starts") = false,
+           py::arg("betas") = py::none())
         .def_property_readonly("series_stats", [](sart::MultiFrameEngine& e) {
             const auto& s = e.series_stats();
             py::dict d;
@@ -895,6 +908,15 @@ PYBIND11_MODULE(_sart_hip, m) {
     }, py::arg("row_ptr"), py::arg("col"), py::arg("val"), py::arg("nnz"), py::arg("nrows"), py::arg("nvoxel"),
        py::arg("ld"), py::arg("X"), py::arg("ldx"), py::arg("nv"), py::arg("Xt"), py::arg("F"), py::arg("ldf"),
        py::arg("stream") = 0, py::arg("lanes") = 0);
+    // squared roughness norms of nv <= 8 fp64 solutions X [nv][ldx] under the Laplacian CSR (n rows); eta2: nv doubles,
+    // scratch: rough64_scratch_elems(n) doubles
+    m.def("rough64_scratch_elems", &sart::rough64_scratch_elems, py::arg("n"));
+    m.def("rough64", [](uintptr_t row_ptr, uintptr_t col, uintptr_t val, int64_t n, uintptr_t X, int64_t ldx, int nv,
+                        bool logx, uintptr_t eta2, uintptr_t scratch, uintptr_t stream) {
+        sart::launch_rough64(P<const int64_t>(row_ptr), P<const int32_t>(col), P<const float>(val), n,
+                             P<const double>(X), ldx, nv, logx, P<double>(eta2), P<double>(scratch), S(stream));
+    }, py::arg("row_ptr"), py::arg("col"), py::arg("val"), py::arg("n"), py::arg("X"), py::arg("ldx"), py::arg("nv"),
+       py::arg("logx"), py::arg("eta2"), py::arg("scratch"), py::arg("stream") = 0);
     m.def("prep_rows", [](uintptr_t g, int64_t nrows, int64_t nrows_pad, double inv_s, uintptr_t ray_length,
                           float len_thres, uintptr_t ghat, uintptr_t arow, uintptr_t gpos, uintptr_t wo,
                           uintptr_t stream) {

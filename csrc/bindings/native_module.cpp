@@ -16,6 +16,7 @@
 #include "frames.hpp"
 #include "h5.hpp"
 #include "inputs.hpp"
+#include "lcurve.hpp"
 
 namespace py = pybind11;
 using namespace sart;
@@ -81,6 +82,7 @@ PYBIND11_MODULE(_sart_native, m) {
         .def_readwrite("fp64_semantics", &Config::fp64_semantics)
         .def_readwrite("fit", &Config::fit)
         .def_readwrite("fit_only", &Config::fit_only)
+        .def_readwrite("beta_scan", &Config::beta_scan)
         .def_readwrite("profile_file", &Config::profile_file)
         .def_readwrite("help", &Config::help);
     m.def("parse_arguments", &parse_arguments, py::arg("argv"));
@@ -251,6 +253,26 @@ PYBIND11_MODULE(_sart_native, m) {
         return py::array_t<double>();
 #endif
     });
+    // a dataset's stored type as a NumPy type string ("<f8", "<i4", "|u1", ...; tests of the file formats)
+    m.def("dataset_dtype", [](const std::string& fn, const std::string& name) {
+#ifdef SART_HAVE_HDF5
+        SART_H5_LOCK;
+        H5Id f = h5_open_file(fn);
+        H5Id d = h5_open_dataset(f, name);
+        H5Id t(H5Dget_type(d), H5Id::kType);
+        const H5T_class_t cls = H5Tget_class(t);
+        const size_t size = H5Tget_size(t);
+        if (cls != H5T_FLOAT && cls != H5T_INTEGER) throw Error("dataset " + name + " is not numeric");
+        const char kind = cls == H5T_FLOAT ? 'f' : (H5Tget_sign(t) == H5T_SGN_NONE ? 'u' : 'i');
+        const char order = size == 1 ? '|' : (H5Tget_order(t) == H5T_ORDER_BE ? '>' : '<');
+        return std::string(1, order) + kind + std::to_string(size);
+#else
+        (void)fn;
+        (void)name;
+        throw Error("built without HDF5 support");
+        return std::string();
+#endif
+    });
 
     py::class_<VoxelGrid>(m, "VoxelGrid")
         .def(py::init<>())
@@ -356,6 +378,14 @@ PYBIND11_MODULE(_sart_native, m) {
         }
         return F;
     }, py::arg("nrows"), py::arg("ncols"), py::arg("ptr"), py::arg("idx"), py::arg("val"), py::arg("X"));
+    // L-curve corner of a weight scan (lcurve.hpp): (selected, found, curvature [nb]); points in increasing-weight order
+    m.def("lcurve_corner", [](f64arr rho, f64arr eta, py::array_t<uint8_t, py::array::c_style | py::array::forcecast> ok,
+                              int fallback) {
+        if (rho.ndim() != 1 || eta.size() != rho.size() || ok.size() != rho.size())
+            throw py::value_error("rho, eta and ok must be vectors of one length");
+        const LcurveCorner c = lcurve_corner(rho.data(), eta.data(), ok.data(), (int)rho.size(), fallback);
+        return py::make_tuple(c.selected, c.found, py::array_t<double>(c.curvature.size(), c.curvature.data()));
+    }, py::arg("rho"), py::arg("eta"), py::arg("ok"), py::arg("fallback"));
     m.def("fit_statistics", [](f64arr f, f64arr g, f64arr ell, double threshold, const std::vector<int64_t>& camera_pixels) {
         if (f.size() != g.size() || ell.size() != g.size()) throw py::value_error("f, g and ell must have one length");
         FitStats s;

@@ -17,8 +17,10 @@
 // Extensions: --resume, --two_pass, --profile FILE (JSON lines per frame: iterations, convergence, it/s,
 // GFLOPS, RTM GB/s, GPU time in the all-reduces, communicators), --batch_frames N (N
 // frames solved together by the multi-frame MFMA engine; batches warm-start from the previous batch), --fit / --fit_only
-// (after the frames: fp64 fitted images and residuals of every stored solution into the output's /fit group).
-// This file: main()'s sequence and the runs it starts (run_series, run_frames, run_fit_pass). The shard and its
+// (after the frames: fp64 fitted images and residuals of every stored solution into the output's /fit group),
+// --beta_scan B0,B1,... (every frame at each Laplacian weight as columns of the multi-frame engine; the L-curve into
+// the output's /beta_scan group, its corner's solution into /solution).
+// This file: main()'s sequence and the runs it starts (run_series, run_frames, run_fit_pass, run_scan). The shard and its
 // loaders: shard_load.{hpp,cpp}; the series' frame reader: frame_readahead.hpp; the --profile lines: profile_lines.
 #include <algorithm>
 #include <cmath>
@@ -43,6 +45,7 @@
 #include "../native/cpu_solver.hpp"
 #include "../native/fit.hpp"
 #include "../native/frames.hpp"
+#include "../native/lcurve.hpp"
 #include "frame_readahead.hpp"
 #include "profile_lines.hpp"
 #include "shard_load.hpp"
@@ -107,6 +110,7 @@ Solvers build_solvers(const Driver& d, Shard& sh, const SolverParams& params, co
         // batch width 16, 32, 64 or 128 (rounded up; 128: bf16 storage and f16-pair split-A); sparse shards: fp32 SpMM
         // projections of the CSR / CSC; bf16 / f16 shards: MFMA projections
         base.mf_frames = cfg.batch_frames;
+        base.mf_frame_beta = !cfg.beta_scan.empty();  // the scan brings a weight per column: keep the Laplacian
         s.mf = make_engine<MultiFrameEngine>(sh, d.device, d.dcomm.get(), base, lap);
         // a cold time series' first frame: the single-frame engine, built with the set-up (before the frame loop's
         // clock, like the frame-by-frame engine); dropped after that frame (SART_MF_LEAD_ENGINE=0: none)
@@ -313,6 +317,70 @@ void run_frames(Driver& d, Solvers& s, const std::vector<uint64_t>& frames, std:
     }
 }
 
+// solutions per pass over the shard: the width at which a frame costs least for the storage (8; 4 on 16-bit shards)
+int fit_group(const Shard& sh) {
+    const DeviceShard* dn = sh.dense.get();
+    int group = fit64_group(dn && dn->bf16, dn && dn->f16, !dn);
+    if (const char* e = std::getenv("SART_FIT_GROUP"); e && *e) {  // (an A/B knob: the file does not depend on it)
+        group = std::atoi(e);
+        if (group < 1 || group > 8) throw Error(std::string("SART_FIT_GROUP must be within 1 .. 8, not '") + e + "'");
+    }
+    return group;
+}
+
+// The fit projection of this rank's shard (run_fit_pass, run_scan_pass): device operands X [group][ldx], F [group][ldf]
+// and the sparse kernel's voxel-major copy of X
+struct FitProjector {
+    const Driver& d;
+    const Shard& sh;
+    const int group;
+    DeviceArray<double> dX, dF, dXt;
+    int64_t ldx = 0, ldf = 0;
+    SparseRtm view;
+    FitProjector(const Driver& d_, const Shard& sh_, int group_) : d(d_), sh(sh_), group(group_) {
+        const DeviceShard* dn = sh.dense.get();
+        if (dn) {
+            ldx = dn->ld;
+            ldf = dn->nrows_pad;
+        } else if (sh.sparse) {
+            ldx = (sh.sparse->nvoxel + 63) / 64 * 64;
+            ldf = (sh.sparse->nrows + 63) / 64 * 64;
+            dXt.resize((size_t)ldx * 8);
+            view = sh.sparse->view();
+        }
+        if (sh.gpu) {
+            dX.resize((size_t)group * ldx);
+            dF.resize((size_t)group * ldf);
+        }
+    }
+    // out [n][npixel] += this rank's part of A X^T for X [n][nvoxel] (out zero-filled by the caller); on a GPU shard
+    // dX keeps this rank's voxels of the n solutions afterwards
+    void project(const double* X, int n, double* out) {
+        const uint64_t npixel = d.in.npixel, nvoxel = d.in.nvoxel;
+        const Block &blk = d.blk, &vblk = d.vblk;
+        const DeviceShard* dn = sh.dense.get();
+        if (sh.gpu) {
+            for (int j = 0; j < n; ++j)
+                hip_ok(hipMemcpy(dX.get() + (size_t)j * ldx, X + (size_t)j * nvoxel + vblk.offset,
+                                 vblk.size * sizeof(double), hipMemcpyHostToDevice), "H2D fit solutions");
+            if (dn)
+                launch_fit64(dn->A, dn->bf16, dn->f16, dn->rsc.get(), dn->ld, dn->nrows, dn->nrows_pad, dn->nvoxel,
+                             dX.get(), ldx, n, dF.get(), ldf, nullptr);
+            else
+                launch_fit64_csr(view, sh.sparse->nrows, sh.sparse->nvoxel, ldx, dX.get(), ldx, n, dXt.get(), dF.get(),
+                                 ldf, nullptr);
+            for (int j = 0; j < n; ++j)
+                hip_ok(hipMemcpy(out + (size_t)j * npixel + blk.offset, dF.get() + (size_t)j * ldf,
+                                 blk.size * sizeof(double), hipMemcpyDeviceToHost), "D2H fitted images");
+        } else if (sh.csr_format) {
+            cpu_fit_forward(sh.csr, X, (int64_t)nvoxel, n, out + blk.offset, (int64_t)npixel);
+        } else {
+            cpu_fit_forward(sh.host.data(), (int64_t)blk.size, (int64_t)nvoxel, (int64_t)nvoxel, X, (int64_t)nvoxel, n,
+                            out + blk.offset, (int64_t)npixel);
+        }
+    }
+};
+
 // --fit / --fit_only: the fitted images f = A x (fp64) of every solution stored in the output file, in groups of up to
 // 8 per pass over the shard (4 on bf16 / f16 shards; SART_FIT_GROUP overrides), and their residuals against the
 // measured composite frames, into the file's /fit group (docs/FORMATS.md). Main thread, after the frame loop, with the
@@ -325,7 +393,6 @@ void run_fit_pass(Driver& d, const Shard& sh) {
     const InputSet& in = d.in;
     HostComm* host = d.host;
     const CompositeImage& image = *d.image;
-    const Block &blk = d.blk, &vblk = d.vblk;
     const auto t_fit = Clock::now();
     const uint64_t npixel = in.npixel, nvoxel = in.nvoxel;
     std::vector<double> times;
@@ -350,57 +417,13 @@ void run_fit_pass(Driver& d, const Shard& sh) {
         }
         frame_of[k] = i;
     }
-    const DeviceShard* dn = sh.dense.get();
-    // solutions per pass over the shard: the width at which a frame costs least for the storage (8; 4 on 16-bit shards)
-    int group = fit64_group(dn && dn->bf16, dn && dn->f16, !dn);
-    if (const char* e = std::getenv("SART_FIT_GROUP"); e && *e) {  // (an A/B knob: the file does not depend on it)
-        group = std::atoi(e);
-        if (group < 1 || group > 8) throw Error(std::string("SART_FIT_GROUP must be within 1 .. 8, not '") + e + "'");
-    }
-    // device operands: X [group][ldx], F [group][ldf], the sparse kernel's voxel-major copy of X
-    DeviceArray<double> dX, dF, dXt;
-    int64_t ldx = 0, ldf = 0;
-    SparseRtm view;
-    if (dn) {
-        ldx = dn->ld;
-        ldf = dn->nrows_pad;
-    } else if (sh.sparse) {
-        ldx = (sh.sparse->nvoxel + 63) / 64 * 64;
-        ldf = (sh.sparse->nrows + 63) / 64 * 64;
-        dXt.resize((size_t)ldx * 8);
-        view = sh.sparse->view();
-    }
-    if (sh.gpu) {
-        dX.resize((size_t)group * ldx);
-        dF.resize((size_t)group * ldf);
-    }
-    // out [n][npixel] += this rank's part of A X^T for X [n][nvoxel] (out zero-filled by the caller)
-    auto project = [&](const double* X, int n, double* out) {
-        if (sh.gpu) {
-            for (int j = 0; j < n; ++j)
-                hip_ok(hipMemcpy(dX.get() + (size_t)j * ldx, X + (size_t)j * nvoxel + vblk.offset,
-                                 vblk.size * sizeof(double), hipMemcpyHostToDevice), "H2D fit solutions");
-            if (dn)
-                launch_fit64(dn->A, dn->bf16, dn->f16, dn->rsc.get(), dn->ld, dn->nrows, dn->nrows_pad, dn->nvoxel,
-                             dX.get(), ldx, n, dF.get(), ldf, nullptr);
-            else
-                launch_fit64_csr(view, sh.sparse->nrows, sh.sparse->nvoxel, ldx, dX.get(), ldx, n, dXt.get(), dF.get(),
-                                 ldf, nullptr);
-            for (int j = 0; j < n; ++j)
-                hip_ok(hipMemcpy(out + (size_t)j * npixel + blk.offset, dF.get() + (size_t)j * ldf,
-                                 blk.size * sizeof(double), hipMemcpyDeviceToHost), "D2H fitted images");
-        } else if (sh.csr_format) {
-            cpu_fit_forward(sh.csr, X, (int64_t)nvoxel, n, out + blk.offset, (int64_t)npixel);
-        } else {
-            cpu_fit_forward(sh.host.data(), (int64_t)blk.size, (int64_t)nvoxel, (int64_t)nvoxel, X, (int64_t)nvoxel, n,
-                            out + blk.offset, (int64_t)npixel);
-        }
-    };
+    FitProjector fp(d, sh, fit_group(sh));
+    const int group = fp.group;
     // the ray lengths: the fit projection of the all-ones vector (one extra pass; any storage, no engine needed)
     std::vector<double> ell(npixel, 0.0);
     {
         const std::vector<double> ones(nvoxel, 1.0);
-        project(ones.data(), 1, ell.data());
+        fp.project(ones.data(), 1, ell.data());
         host->all_reduce_host(ell.data(), ell.size(), ReduceOp::kSum);
     }
     std::unique_ptr<FitWriter> fw;
@@ -425,7 +448,7 @@ void run_fit_pass(Driver& d, const Shard& sh) {
         }
         host->broadcast_host(X.data(), (size_t)n * nvoxel * sizeof(double), 0);
         std::fill(F.begin(), F.begin() + (size_t)n * npixel, 0.0);
-        project(X.data(), n, F.data());
+        fp.project(X.data(), n, F.data());
         host->all_reduce_host(F.data(), (size_t)n * npixel, ReduceOp::kSum);
         if (d.rank == 0)
             for (int j = 0; j < n; ++j) {
@@ -441,6 +464,136 @@ void run_fit_pass(Driver& d, const Shard& sh) {
         std::cout << "Fit of " << T << " frame(s) in: " << ms << " ms" << std::endl;
         if (d.profile.is_open()) write_fit_line(d.profile, T, groups, ms, sh.storage, sh.format, d.size);
     }
+}
+
+// --beta_scan: what rank 0 keeps of the columns between the series and the scan pass (the solutions are in the file)
+struct ScanColumns {
+    std::unique_ptr<ScanWriter> file;       // rank 0
+    std::vector<int32_t> status, iterations;  // [T nb], rank 0
+    std::vector<uint8_t> ok;                  // [T nb], rank 0: the column did not stop on a non-finite iterate
+};
+
+// --beta_scan, the frame loop: run_series over T nb virtual frames, virtual frame j = k nb + i being composite frame k
+// at weight i, all cold columns of the multi-frame engine with a weight per column. Rank 0's sink writes every
+// finished column into /beta_scan as it arrives (no host collective in the sink: the series thread interleaves staging
+// and delivery differently on different ranks); nothing goes to /solution yet.
+void run_scan_series(Driver& d, Solvers& s, const std::vector<uint64_t>& frames, ScanColumns& sc) {
+    const Config& cfg = d.cfg;
+    const int64_t nb = (int64_t)cfg.beta_scan.size(), T = (int64_t)frames.size(), nvirt = T * nb;
+    FrameReadahead ra(nvirt, 4 * (int64_t)cfg.batch_frames,
+                      [&](int64_t j) { return d.image->frame(frames[j / nb]); });  // (the image caches its frames)
+    const size_t npix = (size_t)s.mf->nrows();
+    auto src = [&](int64_t j, double* dst) {
+        const std::vector<double> f = ra.take(j);
+        if (f.size() != npix) throw std::runtime_error("frame size does not match the shard's pixels");
+        std::copy(f.begin(), f.end(), dst);
+    };
+    std::vector<float> frame_beta((size_t)nvirt);
+    for (int64_t j = 0; j < nvirt; ++j) frame_beta[j] = (float)cfg.beta_scan[j % nb];
+    std::vector<int64_t> left((size_t)T, nb);  // columns of each composite frame still to come
+    double sink_ms = 0.0;
+    auto t_prev = Clock::now();
+    auto sink = [&](int64_t j, const double* xs, const SolveInfo& info) {
+        if (d.rank != 0) return;
+        const auto tsk = Clock::now();
+        const int64_t k = j / nb, i = j % nb;
+        sc.file->write_column((uint64_t)k, (uint64_t)i, xs, info.status, info.iterations);
+        sc.status[j] = info.status, sc.iterations[j] = info.iterations, sc.ok[j] = info.nonfinite ? 0 : 1;
+        if (info.nonfinite)
+            std::cerr << "warning: frame " << frames[k] << ", beta " << cfg.beta_scan[i]
+                      << ": non-finite iterate, stopped" << std::endl;
+        if (--left[k] == 0) {
+            const auto now = Clock::now();
+            std::cout << "Processed in: " << std::chrono::duration<double, std::milli>(now - t_prev).count() << " ms"
+                      << std::endl;
+            t_prev = now;
+        }
+        sink_ms += ms_since(tsk);
+    };
+    s.mf->solve_series(nvirt, src, sink, nullptr, false, frame_beta.data());
+    if (d.rank == 0) sc.file->close();
+    if (d.rank == 0 && d.profile.is_open()) write_series_line(d.profile, *s.mf, ra.reader_ms(), sink_ms);
+}
+
+// --beta_scan, after the loop (main thread, shaped like run_fit_pass): the rows of /beta_scan/value in groups of
+// fit_group() -- rank 0 reads and broadcasts a group, every rank projects it on its shard, the images are summed over
+// the ranks through the zero-filled host all-reduce, rank 0 takes the residual norm against the frame's measured
+// pixels (the /fit/residual_norm definition) and the roughness norm of the same device copy of the group
+// (csrc/kernels/rough64.hip). A frame whose nb points are complete gets its corner (lcurve_corner); the selected
+// column goes to /solution through the ordinary writer, in frame order.
+void run_scan_pass(Driver& d, const Shard& sh, const Csr& lap, const std::vector<uint64_t>& frames, ScanColumns& sc) {
+    const Config& cfg = d.cfg;
+    HostComm* host = d.host;
+    const CompositeImage& image = *d.image;
+    const auto t_scan = Clock::now();
+    const uint64_t npixel = d.in.npixel, nvoxel = d.in.nvoxel;
+    const uint64_t nb = cfg.beta_scan.size(), T = frames.size(), nvirt = T * nb;
+    // -b names the fallback: the ladder entry nearest to it (ties to the smaller)
+    int fallback = 0;
+    for (uint64_t i = 1; i < nb; ++i)
+        if (std::abs(cfg.beta_scan[i] - cfg.beta_laplace) < std::abs(cfg.beta_scan[fallback] - cfg.beta_laplace))
+            fallback = (int)i;
+    FitProjector fp(d, sh, fit_group(sh));
+    const int group = fp.group;
+    std::vector<double> ell(npixel, 0.0);
+    {
+        const std::vector<double> ones(nvoxel, 1.0);
+        fp.project(ones.data(), 1, ell.data());
+        host->all_reduce_host(ell.data(), ell.size(), ReduceOp::kSum);
+    }
+    std::unique_ptr<CompositeImage> full;  // rank 0: the measured frames over all pixels
+    DeviceArray<int64_t> lrp;
+    DeviceArray<int32_t> lcol;
+    DeviceArray<float> lval;
+    DeviceArray<double> deta2, dscratch;
+    if (d.rank == 0) {
+        full = std::make_unique<CompositeImage>(d.in.image_files, d.in.frame_masks, d.intervals, npixel, 0);
+        full->set_max_cache_size((uint64_t)cfg.max_cached_frames);
+        lrp.resize(nvoxel + 1), lcol.resize((size_t)lap.nnz()), lval.resize((size_t)lap.nnz());
+        hip_ok(hipMemcpy(lrp.get(), lap.row_ptr.data(), (nvoxel + 1) * sizeof(int64_t), hipMemcpyHostToDevice), "H2D");
+        hip_ok(hipMemcpy(lcol.get(), lap.col.data(), (size_t)lap.nnz() * sizeof(int32_t), hipMemcpyHostToDevice), "H2D");
+        hip_ok(hipMemcpy(lval.get(), lap.val.data(), (size_t)lap.nnz() * sizeof(float), hipMemcpyHostToDevice), "H2D");
+        deta2.resize(8);
+        dscratch.resize((size_t)rough64_scratch_elems((int64_t)nvoxel));
+    }
+    const std::vector<int64_t> one_camera{(int64_t)npixel};  // the norm over all pixels does not depend on the split
+    std::vector<double> X((size_t)group * nvoxel), F((size_t)group * npixel), rho(nvirt), eta(nvirt), x(nvoxel), g;
+    uint64_t g_frame = T, decided = 0;  // g: the measured frame g_frame; frames [0, decided) have their corner
+    for (uint64_t j0 = 0; j0 < nvirt; j0 += group) {
+        const int n = (int)std::min<uint64_t>(group, nvirt - j0);
+        if (d.rank == 0) sc.file->read_columns(j0, n, X.data());
+        host->broadcast_host(X.data(), (size_t)n * nvoxel * sizeof(double), 0);
+        std::fill(F.begin(), F.begin() + (size_t)n * npixel, 0.0);
+        fp.project(X.data(), n, F.data());
+        host->all_reduce_host(F.data(), (size_t)n * npixel, ReduceOp::kSum);
+        if (d.rank != 0) continue;
+        for (int j = 0; j < n; ++j) {
+            const uint64_t k = (j0 + j) / nb;
+            if (k != g_frame) g = full->frame(frames[k]), g_frame = k;
+            rho[j0 + j] = fit_statistics(F.data() + (size_t)j * npixel, g.data(), ell.data(), (int64_t)npixel,
+                                         cfg.ray_length_threshold, one_camera).residual_norm;
+        }
+        double eta2[8];
+        launch_rough64(lrp.get(), lcol.get(), lval.get(), (int64_t)nvoxel, fp.dX.get(), fp.ldx, n, cfg.logarithmic,
+                       deta2.get(), dscratch.get(), nullptr);
+        hip_ok(hipMemcpy(eta2, deta2.get(), (size_t)n * sizeof(double), hipMemcpyDeviceToHost), "D2H roughness");
+        for (int j = 0; j < n; ++j) eta[j0 + j] = std::sqrt(eta2[j]);
+        for (; (decided + 1) * nb <= j0 + n; ++decided) {
+            const uint64_t k = decided, cur = frames[k];
+            const LcurveCorner c = lcurve_corner(rho.data() + k * nb, eta.data() + k * nb, sc.ok.data() + k * nb,
+                                                 (int)nb, fallback);
+            sc.file->write_frame(k, rho.data() + k * nb, eta.data() + k * nb, c.curvature.data(), c.selected,
+                                 (uint8_t)c.found);
+            const uint64_t js = k * nb + (uint64_t)c.selected;
+            sc.file->read_columns(js, 1, x.data());  // the stored row itself: /solution/value[k] is its bits
+            sc.file->close();                        // the solution writer opens the file itself
+            d.writer->add(x, sc.status[js], image.frame_time(cur), image.camera_frame_time(cur), sc.iterations[js]);
+        }
+    }
+    host->barrier();
+    if (d.rank == 0)
+        std::cout << "Beta scan of " << T << " frame(s) x " << nb << " weights in: " << ms_since(t_scan) << " ms"
+                  << std::endl;
 }
 
 // GPU runs: this rank's device and the device communicator; --use_cpu: the host communicator alone
@@ -493,8 +646,10 @@ void open_output(Driver& d, Resume& r) {
                 r.warm = stored.last_solution;
             }
         }
+        // --beta_scan: the scan creates the file with its /beta_scan group; /solution is added to it
         d.writer = std::make_unique<SolutionWriter>(cfg.output_file, d.in.camera_names, d.in.nvoxel,
-                                                    (uint64_t)cfg.max_cached_solutions, r.appended);
+                                                    (uint64_t)cfg.max_cached_solutions, r.appended,
+                                                    !cfg.beta_scan.empty());
         r.voxelgrid.read(d.in.rtm_files.begin()->second, "rtm/voxel_map");
         for (const auto& m : r.voxelgrid.warnings) std::cerr << "warning: " << m << std::endl;
     }
@@ -577,7 +732,18 @@ void run(Driver& d) {
     for (uint64_t i = 0; i < d.image->nframe(); ++i)
         if (solve && d.image->frame_time(i) > res.skip_until + 1e-12) frames.push_back(i);
     const auto t_loop = Clock::now();
-    if (batched)
+    if (!cfg.beta_scan.empty()) {
+        ScanColumns sc;
+        if (rank == 0) {
+            const size_t nvirt = frames.size() * cfg.beta_scan.size();
+            sc.file = std::make_unique<ScanWriter>(cfg.output_file, frames.size(), cfg.beta_scan.size(), in.nvoxel,
+                                                   cfg.beta_scan.data());
+            sc.status.resize(nvirt), sc.iterations.resize(nvirt), sc.ok.resize(nvirt);
+        }
+        run_scan_series(d, solvers, frames, sc);
+        solvers.reset();  // the engine's device buffers, before the pass allocates its own
+        run_scan_pass(d, shard, lap, frames, sc);
+    } else if (batched)
         run_series(d, solvers, frames, res.warm);
     else
         run_frames(d, solvers, frames, res.warm);

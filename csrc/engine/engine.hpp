@@ -49,6 +49,9 @@ struct EngineConfig : SolverParams {
     int fault_nan_sweep = -1;
     // Multi-frame engine: frames per batch (16, 32, 64 or 128; MultiFrameEngine rounds other values up).
     int mf_frames = 16;
+    // Multi-frame engine: the series will bring a Laplacian weight per frame (solve_series' frame_beta), so
+    // set_laplacian keeps the Laplacian whatever beta_laplace is (a table entry of 0 gives a zero penalty).
+    bool mf_frame_beta = false;
     // Column (voxel) shard instead of the reference's row (pixel) shard: this rank holds ALL
     // pixel rows for voxels [col_offset, col_offset + nvoxel) of nvoxel_total, and gets the full
     // measurement. Per sweep the partial forward projections (a pixel vector) are all-reduced instead of

@@ -183,7 +183,8 @@ void MultiFrameEngine::set_device() const { hip_ok(hipSetDevice(device_), "hipSe
 void MultiFrameEngine::set_laplacian(const int64_t* row_ptr, const int32_t* col, const float* val, int64_t nnz) {
     set_device();
     has_lap_ = false;
-    if (nnz <= 0 || cfg_.beta_laplace <= 0) return;
+    // a weight per frame will come with the series (mf_frame_beta): kept whatever the scalar weight is
+    if (nnz <= 0 || (cfg_.beta_laplace <= 0 && !cfg_.mf_frame_beta)) return;
     if (row_ptr[V_] != nnz) throw std::invalid_argument("Laplacian CSR row pointer does not match nnz");
     lap_rp_.resize(V_ + 1);
     lap_col_.resize(nnz);
@@ -331,7 +332,7 @@ void MultiFrameEngine::sweep() {
     const float* pen = nullptr;
     if (has_lap_) {  // needs X only: runs while the last chunks are being reduced
         launch_mf_penalty(lap_rp_.get(), lap_col_.get(), lap_val_.get(), V_, (float)cfg_.beta_laplace,
-                          cfg_.logarithmic, X_.get(), ld_, pen_.get(), st, NF, stream_);
+                          cfg_.logarithmic, X_.get(), ld_, pen_.get(), st, NF, stream_, beta_dev_, q);
         pen = pen_.get();
     }
     if (comm_->size() > 1 && nc > 1) hip_ok(hipStreamWaitEvent(stream_, comm_done_, 0), "wait all-reduce");
@@ -353,7 +354,8 @@ void MultiFrameEngine::run_chunk() {
     const int chunk = plan_.chunk;
     const bool graphable = plan_.use_graph && !graph_failed_ && warm_chunk_ && comm_->size() == 1 &&
                            comm_->graph_capturable() && cfg_.fault_nan_sweep < 0;
-    if (graph_ && (!graphable || std::memcmp(&graph_rf_, &rf_, sizeof(rf_)) != 0)) drop_graph();
+    if (graph_ && (!graphable || std::memcmp(&graph_rf_, &rf_, sizeof(rf_)) != 0 || graph_beta_ != beta_dev_))
+        drop_graph();
     if (graphable && !graph_) {
         hipGraph_t g = nullptr;
         bool ok = hipStreamBeginCapture(stream_, hipStreamCaptureModeThreadLocal) == hipSuccess;
@@ -373,6 +375,7 @@ void MultiFrameEngine::run_chunk() {
             graph_failed_ = true;
         } else {
             graph_rf_ = rf_;
+            graph_beta_ = beta_dev_;
         }
     }
     if (graphable && graph_) {
@@ -448,7 +451,7 @@ void MultiFrameEngine::stage(int64_t first, int64_t e0, int k, const FrameSource
 }
 
 std::vector<SolveInfo> MultiFrameEngine::solve_batch(const double* g, int nframes, double* x_out, const double* x0,
-                                                     bool chain, double* starts) {
+                                                     bool chain, double* starts, const float* frame_beta) {
     std::vector<SolveInfo> out(std::max(nframes, 0));
     if (nframes <= 0) return out;
     const auto t0 = std::chrono::steady_clock::now();
@@ -464,7 +467,7 @@ std::vector<SolveInfo> MultiFrameEngine::solve_batch(const double* g, int nframe
                 std::memcpy(x_out + k * V_, x, (size_t)V_ * sizeof(double));
                 out[k] = info;
             },
-            x0, chain);
+            x0, chain, frame_beta);
     } catch (...) {
         rf_.starts = nullptr;
         throw;
@@ -483,12 +486,30 @@ std::vector<SolveInfo> MultiFrameEngine::solve_batch(const double* g, int nframe
 }
 
 void MultiFrameEngine::solve_series(int64_t nframes, const FrameSource& src, const FrameSink& sink, const double* x0,
-                                    bool chain) {
+                                    bool chain, const float* frame_beta) {
     set_device();
     RoctxRange range("sart::mf_series");
     stats_ = SeriesStats{};
+    if (frame_beta && chain)
+        throw std::invalid_argument("MultiFrameEngine: a weight per frame needs cold or x0 starts (chain would start a "
+                                    "frame from a neighbour solved at another weight)");
+    if (frame_beta && !has_lap_)
+        throw std::invalid_argument("MultiFrameEngine: a weight per frame needs the Laplacian "
+                                    "(EngineConfig::mf_frame_beta before set_laplacian)");
+    beta_dev_ = nullptr;
     if (nframes <= 0) return;
     if (nframes > std::numeric_limits<int32_t>::max()) throw std::invalid_argument("solve_series: too many frames");
+    if (frame_beta) {
+        // once per series, indexed by the series' frame (MfQueue::slot_frame) through refills, graph replays and a
+        // restarted pass alike; the previous series has been synchronised, so the table can be replaced
+        for (int64_t k = 0; k < nframes; ++k)
+            if (!(frame_beta[k] >= 0.f) || !std::isfinite(frame_beta[k]))
+                throw std::invalid_argument("MultiFrameEngine: frame weights must be finite and >= 0");
+        if ((int64_t)beta_tab_.size() < nframes) beta_tab_.resize((size_t)nframes);
+        hip_ok(hipMemcpy(beta_tab_.get(), frame_beta, (size_t)nframes * sizeof(float), hipMemcpyHostToDevice),
+               "H2D frame weights");
+        beta_dev_ = beta_tab_.get();
+    }
     const auto t0 = std::chrono::steady_clock::now();
     std::vector<char> delivered((size_t)nframes, 0);
     frame_norm_.assign((size_t)nframes, 1.0);

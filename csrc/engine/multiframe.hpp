@@ -47,14 +47,19 @@ class MultiFrameEngine {
     // batch_frames() frames (!chain); null: cold. chain (time series): every frame starts from the current iterate
     // of the newest frame in flight or finished (SolveInfo::warm_from / warm_iter), rescaled to its own
     // normalisation; otherwise frames cold-start. Collective over the communicator.
+    // frame_beta (optional, host, nframes entries): frame k's Laplacian weight, the k of src / sink, copied to the
+    // device once per series; null: cfg.beta_laplace for every frame. The engine needs its Laplacian for it
+    // (EngineConfig::mf_frame_beta keeps it whatever beta_laplace is); an entry of 0 gives a zero penalty. Refused
+    // with chain (std::invalid_argument): a warm chain would start a frame from a neighbour solved at another weight.
     using FrameSource = std::function<void(int64_t k, double* dst)>;
     using FrameSink = std::function<void(int64_t k, const double* x, const SolveInfo& info)>;
     void solve_series(int64_t nframes, const FrameSource& src, const FrameSink& sink, const double* x0 = nullptr,
-                      bool chain = false);
+                      bool chain = false, const float* frame_beta = nullptr);
     // g: nframes x nrows (host fp64, frame-major); x_out: nframes x nvoxel: solve_series over an array.
     // starts (optional, nframes x nvoxel): each frame's start value, de-normalised (tests of the chain semantics)
     std::vector<SolveInfo> solve_batch(const double* g, int nframes, double* x_out, const double* x0 = nullptr,
-                                       bool chain = false, double* starts = nullptr);
+                                       bool chain = false, double* starts = nullptr,
+                                       const float* frame_beta = nullptr);
     // counters of the last solve_series (--profile): sweeps the device ran with a frame in some slot, sweeps queued,
     // slot-sweeps spent on frames (sum of sweeps per frame) over nf x sweeps, staged frames, restarts
     struct SeriesStats {
@@ -149,6 +154,11 @@ class MultiFrameEngine {
     DeviceArray<int32_t> lap_col_;
     DeviceArray<float> lap_val_;
     bool has_lap_ = false;
+    // the series' per-frame Laplacian weights (solve_series' frame_beta; beta_dev_ null: cfg_.beta_laplace), and the
+    // pointer the captured graph's penalty kernels hold
+    DeviceArray<float> beta_tab_;
+    const float* beta_dev_ = nullptr;
+    const float* graph_beta_ = nullptr;
     // overlapped back-projection / all-reduce (several ranks, plan_.chunks): comm stream, events
     hipStream_t comm_stream_ = nullptr;
     std::vector<hipEvent_t> cev_;

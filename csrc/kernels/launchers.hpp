@@ -143,6 +143,14 @@ void launch_fit64(const void* A, bool bf16, bool f16, const float* row_scale, in
 // shard, so a row's bits do not depend on the row partition); Xt: scratch of ld x 8 doubles (X voxel-major, written here)
 void launch_fit64_csr(const SparseRtm& s, int64_t nrows, int64_t nvoxel, int64_t ld, const double* X, int64_t ldx,
                       int nv, double* Xt, double* F, int64_t ldf, hipStream_t stream);
+// rough64.hip: squared roughness norms eta2[j] = sum_{r < n} (sum_k L[r, col_k] u_j[col_k])^2 of nv <= 8 fp64
+// solutions X [nv][ldx] per pass over the Laplacian CSR (u = x, or log(max(x, 1e-100)) with logx); every product and
+// sum an fp64 FMA, a fixed 8 lanes per row, per-block partial sums into scratch (rough64_scratch_elems(n) doubles),
+// then a fixed-order second stage: no atomics, eta2[j] depends on X[j] alone. Entries of X at and beyond n are not
+// read. eta2_out: nv device doubles.
+int64_t rough64_scratch_elems(int64_t n);
+void launch_rough64(const int64_t* row_ptr, const int32_t* col, const float* val, int64_t n, const double* X,
+                    int64_t ldx, int nv, bool logx, double* eta2_out, double* scratch, hipStream_t stream);
 // sart_update.hip
 void launch_prep_rows(const double* g, int64_t nrows, int64_t nrows_pad, double inv_s, const float* ray_length,
                       float len_thres, float* ghat, float* arow, float* gpos, float* wo, hipStream_t stream);
@@ -367,8 +375,10 @@ void launch_mf_weights(const float* Fs, int nsplit, int64_t nrows_pad, const flo
 // D[v][f] (voxel-major) for v in [v0, v1); F2out (optional) = per-frame sums of F2part
 void launch_mf_collect(const float* part, int nsplit, int64_t ld, int64_t v0, int64_t v1, const float* scale, float* D,
                        const double* F2part, int nF2, float* F2out, int nf, hipStream_t stream);
+// beta_tab (optional, with q): a weight per frame of the series; slot f uses beta_tab[q->slot_frame[f]], else beta
 void launch_mf_penalty(const int64_t* row_ptr, const int32_t* col, const float* val, int64_t n, float beta, bool logx,
-                       const float* X, int64_t ld, float* pen, const MfState* st, int nf, hipStream_t stream);
+                       const float* X, int64_t ld, float* pen, const MfState* st, int nf, hipStream_t stream,
+                       const float* beta_tab = nullptr, const MfQueue* q = nullptr);
 // q (optional): the device refill plan follows the decisions (mf_plan, MultiFrameEngine::solve_series)
 void launch_mf_decide(MfState* st, const float* F2, hipStream_t stream, MfQueue* q = nullptr);
 // Xprev (optional): receives X before the update (NaN/Inf guard rollback). q / rf: the refill of this sweep's plan

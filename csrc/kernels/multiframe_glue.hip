@@ -147,14 +147,23 @@ __global__ __launch_bounds__(256) void k_mf_collect(const float* __restrict__ pa
 // blockIdx.y: a wave reads 64 consecutive CSR rows and the x / pen entries of one frame row (coalesced; with the
 // frame index fastest, every lane read a different frame row: 566 us per 64-frame sweep at 262144 voxels,
 // profiles/rocprof_r4_2tb_kernel_stats.csv), and a finished frame's blocks return at once.
+// beta_tab (with q; null: beta for every slot): a weight per frame of the series, read through the slot's frame index
+// (one uniform load per block); beta * s stays one fp32 multiply, so a table of equal entries gives the scalar's bits.
 __global__ __launch_bounds__(256) void k_mf_penalty(const int64_t* __restrict__ row_ptr, const int32_t* __restrict__ col,
                                                     const float* __restrict__ val, int64_t n, float beta, int logx,
                                                     const float* __restrict__ X, int64_t ld, float* __restrict__ pen,
-                                                    const MfState* __restrict__ st) {
+                                                    const MfState* __restrict__ st,
+                                                    const float* __restrict__ beta_tab,
+                                                    const MfQueue* __restrict__ q) {
     if (st->all_done) return;
     const int f = blockIdx.y;
     const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (r >= n || st->done[f]) return;
+    if (beta_tab) {
+        const int fr = q->slot_frame[f];
+        if (fr < 0) return;  // (an empty slot is done: not reached)
+        beta = beta_tab[fr];
+    }
     const float* x = X + (int64_t)f * ld;
     float s = 0.f;  // same arithmetic as k_penalty_csr (sart_update.hip)
     for (int64_t k = row_ptr[r]; k < row_ptr[r + 1]; ++k) {
@@ -823,10 +832,12 @@ void launch_mf_collect(const float* part, int nsplit, int64_t ld, int64_t v0, in
 
 // The kernels below take nf from the state (set by k_mf_state_begin): nf = frames of the engine's batch.
 void launch_mf_penalty(const int64_t* row_ptr, const int32_t* col, const float* val, int64_t n, float beta, bool logx,
-                       const float* X, int64_t ld, float* pen, const MfState* st, int nf, hipStream_t stream) {
+                       const float* X, int64_t ld, float* pen, const MfState* st, int nf, hipStream_t stream,
+                       const float* beta_tab, const MfQueue* q) {
     check_nf(nf, "mf_penalty");
+    if (beta_tab && !q) throw std::runtime_error("mf_penalty: a weight table needs the queue (the slots' frames)");
     hipLaunchKernelGGL(k_mf_penalty, dim3(nb(n), nf), dim3(256), 0, stream, row_ptr, col, val, n, beta,
-                       logx ? 1 : 0, X, ld, pen, st);
+                       logx ? 1 : 0, X, ld, pen, st, beta_tab, q);
     check_launch("k_mf_penalty");
 }
 

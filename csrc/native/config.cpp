@@ -1,6 +1,7 @@
 #include "config.hpp"
 
 #include <cerrno>
+#include <cmath>
 #include <cstdlib>
 #include <functional>
 #include <limits>
@@ -43,6 +44,27 @@ std::string fmt(double v) {
     std::ostringstream os;
     os << v;
     return os.str();
+}
+
+// "B0,B1,...": 3 .. 64 finite values >= 0 in strictly increasing order; anything else is one error, with the text given
+std::vector<double> to_beta_scan(const std::string& text) {
+    const Error bad("Argument beta_scan must list 3 to 64 increasing values >= 0, " + text + " given.");
+    std::vector<double> out;
+    size_t pos = 0;
+    while (true) {
+        const size_t comma = text.find(',', pos);
+        const std::string t = trim(text.substr(pos, comma == std::string::npos ? std::string::npos : comma - pos));
+        char* end = nullptr;
+        errno = 0;
+        const double v = std::strtod(t.c_str(), &end);
+        if (t.empty() || end != t.c_str() + t.size() || errno == ERANGE || !std::isfinite(v) || v < 0) throw bad;
+        if (!out.empty() && !(v > out.back())) throw bad;
+        out.push_back(v);
+        if (comma == std::string::npos) break;
+        pos = comma + 1;
+    }
+    if (out.size() < 3 || out.size() > 64) throw bad;
+    return out;
 }
 
 }  // namespace
@@ -111,12 +133,22 @@ std::string usage() {
            "  --fit_only                  Solve nothing: load the RTM as the other options say and run the fit pass\n"
            "                              over the solutions already in the output file (e.g. an --rtm_bf16 solution\n"
            "                              against the fp32 matrix). Not with --resume, --batch_frames > 1 or --fp64.\n"
+           "  --beta_scan B0,B1,...       Solve every frame at each of these Laplacian weights (3 to 64 increasing\n"
+           "                              values >= 0) in one batched run: every weight is a column of the\n"
+           "                              multi-frame engine, so the ladder costs about one batch sweep per iteration.\n"
+           "                              Writes the L-curve (residual and roughness norms, curvature) and every\n"
+           "                              solution into the output file's /beta_scan group and the corner's solution\n"
+           "                              into /solution. Needs -l; implies --no_guess and --batch_frames >= 16;\n"
+           "                              -b only names the fallback weight (the nearest entry) when no corner is\n"
+           "                              found. Not with --use_cpu, --fp64, --partition_voxels, --resume, --fit or\n"
+           "                              --fit_only.\n"
            "  --profile FILE              Write per-frame timing/iteration telemetry as JSON lines.\n";
 }
 
 Config parse_arguments(const std::vector<std::string>& argv) {
     Config c;
-    bool semantics_given = false;
+    bool semantics_given = false, scan_given = false;
+    std::string scan_text;
     using Setter = std::function<void(const std::string&, const std::string&)>;
     std::map<std::string, Setter> valued = {
         {"--output_file", [&](const std::string& v, const std::string&) { c.output_file = v; }},
@@ -136,6 +168,7 @@ Config parse_arguments(const std::vector<std::string>& argv) {
         {"--profile", [&](const std::string& v, const std::string&) { c.profile_file = v; }},
         {"--rtm_format", [&](const std::string& v, const std::string&) { c.rtm_format = v; }},
         {"--fp64_semantics", [&](const std::string& v, const std::string&) { c.fp64_semantics = v; semantics_given = true; }},
+        {"--beta_scan", [&](const std::string& v, const std::string&) { scan_text = v; scan_given = true; }},
     };
     std::map<std::string, bool*> flags = {
         {"--logarithmic", &c.logarithmic}, {"--no_guess", &c.no_guess},   {"--use_cpu", &c.use_cpu},
@@ -226,6 +259,17 @@ Config parse_arguments(const std::vector<std::string>& argv) {
     if (c.fit_only && c.batch_frames > 1)
         throw Error("Argument fit_only solves no frame: it cannot be combined with batch_frames > 1.");
     if (c.fit_only && c.fp64) throw Error("Argument fit_only solves no frame: it cannot be combined with fp64.");
+    if (scan_given) {
+        c.beta_scan = to_beta_scan(scan_text);
+        if (c.laplacian_file.empty()) throw Error("Argument beta_scan needs a laplacian_file.");
+        if (c.use_cpu || c.fp64 || c.partition_voxels)
+            throw Error("Argument beta_scan applies to the batched GPU solver with pixel-row shards only.");
+        if (c.resume || c.fit || c.fit_only)
+            throw Error("Argument beta_scan writes its own output: it cannot be combined with resume, fit or fit_only.");
+        // every weight is a cold column of the batch engine: at least its narrowest batch, no lead engine, no chain
+        if (c.batch_frames == 1) c.batch_frames = 16;
+        c.no_guess = true;
+    }
     if (c.input_files.size() < 2)
         throw Error("At least two input file, one with RTM and one with image, are required, " +
                     std::to_string(c.input_files.size()) + " given.");

@@ -3,7 +3,7 @@
 // Same options, short aliases, defaults and validation as the reference CLI (reference
 // arguments.cpp:82-251, arguments.hpp:14-33), with an in-tree parser instead of p-ranav/argparse.
 // Extensions (not in the reference) are marked: --resume, --batch_frames, --two_pass, --partition_voxels,
-// --profile, --fp64, --fp64_semantics, --fit, --fit_only.
+// --profile, --fp64, --fp64_semantics, --fit, --fit_only, --beta_scan.
 #pragma once
 
 #include <array>
@@ -47,6 +47,10 @@ struct Config {
                                          // (what --use_cpu computes)
     bool fit = false;           // after the frames: fp64 fitted images f = A x and residuals into the output's /fit group
     bool fit_only = false;      // no solve: the fit pass alone over the solutions already in the output file
+    // every frame at each of these Laplacian weights in one batched run (3 .. 64 increasing values >= 0): the L-curve
+    // in the output's /beta_scan group, its corner's solution in /solution. Implies batch_frames >= 16 and no_guess;
+    // beta_laplace only names the fallback entry
+    std::vector<double> beta_scan;
     std::string profile_file;   // JSON timing/telemetry sidecar
     bool help = false;
 };

@@ -189,8 +189,9 @@ std::vector<double> CompositeImage::camera_frame_time(uint64_t i) const {
 // SolutionWriter
 // =============================================================================================
 SolutionWriter::SolutionWriter(std::string filename, std::vector<std::string> camera_names, uint64_t nvoxel,
-                               uint64_t max_cache_size, bool append)
-    : filename_(std::move(filename)), cams_(std::move(camera_names)), nvox_(nvoxel), first_(!append) {
+                               uint64_t max_cache_size, bool append, bool into_existing)
+    : filename_(std::move(filename)), cams_(std::move(camera_names)), nvox_(nvoxel), first_(!append),
+      into_existing_(into_existing) {
     if (nvox_ == 0) throw Error("Argument nvoxel must be positive.");
     set_max_cache_size(max_cache_size);
     cache_.cam_times.resize(cams_.size());
@@ -254,7 +255,7 @@ void write_1d_at(hid_t ds, hid_t mtype, hsize_t offset, hsize_t n, const void* d
 
 void SolutionWriter::create(uint64_t chunk) {
     SART_H5_LOCK;
-    H5Id f = h5_create_file(filename_);
+    H5Id f = into_existing_ ? h5_open_file(filename_, true) : h5_create_file(filename_);
     H5Id g = h5_create_group(f, "solution");
     const hsize_t n = chunk;
     {

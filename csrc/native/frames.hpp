@@ -60,7 +60,7 @@ class CompositeImage {
 class SolutionWriter {
    public:
     SolutionWriter(std::string filename, std::vector<std::string> camera_names, uint64_t nvoxel,
-                   uint64_t max_cache_size = 100, bool append = false);
+                   uint64_t max_cache_size = 100, bool append = false, bool into_existing = false);
     ~SolutionWriter();
     void add(const std::vector<double>& solution, int32_t status, double time, const std::vector<double>& camera_time,
              int32_t iterations = -1);
@@ -84,6 +84,7 @@ class SolutionWriter {
     std::vector<std::string> cams_;
     uint64_t nvox_, max_cache_;
     bool first_;
+    bool into_existing_;  // the first write adds /solution to the file as it is (--beta_scan) instead of creating it
     Batch cache_;
     // a full cache is written by a background thread (one at a time) while the frame loop continues: the
     // max_cache_size-frame flush no longer stalls the frame that fills the cache (profiles/series_r5_*.jsonl)

@@ -42,7 +42,8 @@ MAX_BATCH = 128  # widest batch: 8 column groups (bf16 storage and split-A with 
 class MultiFrameSARTSolver:
     def __init__(self, rtm, laplacian: Optional[LaplacianCSR] = None, comm: Optional[Communicator] = None,
                  params: Optional[SolverParams] = None, logarithmic: bool = False, batch: int = NF,
-                 check_interval: int = 16, allow_zero_tolerance: bool = False, split_a: Optional[bool] = None):
+                 check_interval: int = 16, allow_zero_tolerance: bool = False, split_a: Optional[bool] = None,
+                 frame_betas: bool = False):
         if getattr(rtm, "is_column_shard", False):
             raise NotImplementedError("the multi-frame engine runs on row shards (use SARTSolver for column shards)")
         self.k = hip()
@@ -53,7 +54,11 @@ class MultiFrameSARTSolver:
         self.params.validate(allow_zero_tolerance)
         self.log = bool(logarithmic)
         self.batch = max(1, min(int(batch), MAX_BATCH))
-        self.L = laplacian if (laplacian is not None and laplacian.nnz > 0 and self.params.beta_laplace > 0) else None
+        # frame_betas: solve_batch will bring a Laplacian weight per frame (``betas``), so the Laplacian is kept
+        # whatever ``params.beta_laplace`` is (EngineConfig.mf_frame_beta)
+        self.frame_betas = bool(frame_betas)
+        self.L = laplacian if (laplacian is not None and laplacian.nnz > 0 and
+                               (self.params.beta_laplace > 0 or self.frame_betas)) else None
         if self.L is not None and self.L.n != rtm.nvoxel:
             raise ValueError("Laplacian and ray-transfer matrices have different number of voxels.")
         p = self.params
@@ -68,6 +73,7 @@ class MultiFrameSARTSolver:
         cfg.allow_zero_tolerance = bool(allow_zero_tolerance)
         cfg.check_interval = max(1, int(check_interval))
         cfg.mf_frames = self.batch
+        cfg.mf_frame_beta = self.frame_betas
         cfg.rtm_bf16 = bool(getattr(rtm, "is_bf16", False))  # bf16 storage: bf16 MFMA projections
         if getattr(rtm, "is_f16", False):  # row-scaled f16 storage: the same kernels on the f16 MFMA ("f16-storage")
             cfg.rtm_f16 = True
@@ -94,18 +100,28 @@ class MultiFrameSARTSolver:
         self.forward_split = str(self.engine.forward_split)
         self.backproject_split = str(self.engine.backproject_split)
 
-    def solve_batch(self, measurements, x0=None, chain: bool = False, record_starts: bool = False) -> List[SolveResult]:
+    def solve_batch(self, measurements, x0=None, chain: bool = False, record_starts: bool = False,
+                    betas=None) -> List[SolveResult]:
         """Frames [nframes, local pixels] through ``batch_width`` slots refilled on the device. ``x0`` (nvoxel,
         optional): with ``chain`` the start value while no frame is in flight yet, else of the first
         ``batch_width`` frames (None: cold). ``chain``: a time series -- every frame starts from the current
         iterate of the newest frame in flight or finished (``SolveResult.warm_from`` / ``warm_iter``); otherwise
         frames cold-start. ``record_starts``: keep every frame's start value (de-normalised) in ``self.starts``
-        (tests of the chain). ``self.series_stats``: sweeps, slot utilisation, mean iterations of the run."""
+        (tests of the chain). ``betas`` (optional, one float per frame): frame k is solved with the Laplacian weight
+        ``betas[k]`` instead of ``params.beta_laplace`` (0: no penalty); needs a solver built with a Laplacian and
+        ``frame_betas=True`` (or ``beta_laplace > 0``), and is refused with ``chain`` -- a warm chain would start a
+        frame from a neighbour solved at another weight. ``self.series_stats``: sweeps, slot utilisation, mean
+        iterations of the run."""
         g_all = np.ascontiguousarray(np.asarray(measurements, dtype=np.float64))
         if g_all.ndim == 1:
             g_all = g_all[None]
         warm = None if x0 is None else _host_f64(x0)
-        ret = self.engine.solve_batch(g_all, warm, bool(chain), bool(record_starts))
+        btab = None
+        if betas is not None:
+            btab = np.ascontiguousarray(np.asarray(betas, dtype=np.float32).ravel())
+            if btab.size != g_all.shape[0]:
+                raise ValueError("betas must have one entry per frame")
+        ret = self.engine.solve_batch(g_all, warm, bool(chain), bool(record_starts), btab)
         x, infos = ret[0], ret[1]
         self.starts = ret[2] if record_starts else None
         self.series_stats = dict(self.engine.series_stats)
