@@ -917,6 +917,23 @@ PYBIND11_MODULE(_sart_hip, m) {
                              P<const double>(X), ldx, nv, logx, P<double>(eta2), P<double>(scratch), S(stream));
     }, py::arg("row_ptr"), py::arg("col"), py::arg("val"), py::arg("n"), py::arg("X"), py::arg("ldx"), py::arg("nv"),
        py::arg("logx"), py::arg("eta2"), py::arg("scratch"), py::arg("stream") = 0);
+    // replicas r0 .. r0 + nrep - 1 (nrep <= 64) of the n device pixels g into out [nrep][ldo]; time_bits: the frame
+    // time's IEEE-754 bits
+    m.def("noise_replicas", [](uintptr_t g, int64_t n, uint64_t pixel0, uint64_t time_bits, uint32_t r0, int nrep,
+                               double abs_, double shot, double rel, uint64_t seed, uintptr_t out, int64_t ldo,
+                               uintptr_t stream) {
+        sart::launch_noise_replicas(P<const double>(g), n, pixel0, time_bits, r0, nrep, abs_, shot, rel, seed,
+                                    P<double>(out), ldo, S(stream));
+    }, py::arg("g"), py::arg("n"), py::arg("pixel0"), py::arg("time_bits"), py::arg("r0"), py::arg("nrep"),
+       py::arg("abs"), py::arg("shot"), py::arg("rel"), py::arg("seed"), py::arg("out"), py::arg("ldo"),
+       py::arg("stream") = 0);
+    // per-voxel mean and unbiased std over the rows of X [n][ldx] with use[r] != 0 (device uint8)
+    m.def("moments64", [](uintptr_t X, int64_t ldx, int64_t nvoxel, int n, uintptr_t use, uintptr_t mean,
+                          uintptr_t std_out, uintptr_t stream) {
+        sart::launch_moments64(P<const double>(X), ldx, nvoxel, n, P<const uint8_t>(use), P<double>(mean),
+                               P<double>(std_out), S(stream));
+    }, py::arg("X"), py::arg("ldx"), py::arg("nvoxel"), py::arg("n"), py::arg("use"), py::arg("mean"), py::arg("std"),
+       py::arg("stream") = 0);
     m.def("prep_rows", [](uintptr_t g, int64_t nrows, int64_t nrows_pad, double inv_s, uintptr_t ray_length,
                           float len_thres, uintptr_t ghat, uintptr_t arow, uintptr_t gpos, uintptr_t wo,
                           uintptr_t stream) {

@@ -2,6 +2,9 @@
 // CLI/config, time intervals, HDF5 input validation and loaders, composite-image streamer, solution
 // writer, voxel grids, fp64 CPU kernels and HDF5 fixture writers. Long-running calls release the GIL
 // so the Python driver can prefetch the next frame / RTM block while the GPU works.
+#include <array>
+#include <cstring>
+
 #include <pybind11/numpy.h>
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
@@ -17,6 +20,7 @@
 #include "h5.hpp"
 #include "inputs.hpp"
 #include "lcurve.hpp"
+#include "../kernels/philox.hpp"
 
 namespace py = pybind11;
 using namespace sart;
@@ -83,6 +87,12 @@ PYBIND11_MODULE(_sart_native, m) {
         .def_readwrite("fit", &Config::fit)
         .def_readwrite("fit_only", &Config::fit_only)
         .def_readwrite("beta_scan", &Config::beta_scan)
+        .def_readwrite("replicas", &Config::replicas)
+        .def_readwrite("noise_abs", &Config::noise_abs)
+        .def_readwrite("noise_shot", &Config::noise_shot)
+        .def_readwrite("noise_rel", &Config::noise_rel)
+        .def_readwrite("noise_seed", &Config::noise_seed)
+        .def_readwrite("replicas_keep", &Config::replicas_keep)
         .def_readwrite("profile_file", &Config::profile_file)
         .def_readwrite("help", &Config::help);
     m.def("parse_arguments", &parse_arguments, py::arg("argv"));
@@ -386,6 +396,26 @@ PYBIND11_MODULE(_sart_native, m) {
         const LcurveCorner c = lcurve_corner(rho.data(), eta.data(), ok.data(), (int)rho.size(), fallback);
         return py::make_tuple(c.selected, c.found, py::array_t<double>(c.curvature.size(), c.curvature.data()));
     }, py::arg("rho"), py::arg("eta"), py::arg("ok"), py::arg("fallback"));
+    // the noise definition of --replicas (kernels/philox.hpp: the text the noise kernel compiles)
+    m.def("philox4x32_10", [](const std::array<uint32_t, 4>& counter, const std::array<uint32_t, 2>& key) {
+        const Philox4 o = philox4x32_10(counter[0], counter[1], counter[2], counter[3], key[0], key[1]);
+        return py::make_tuple(o.w[0], o.w[1], o.w[2], o.w[3]);
+    }, py::arg("counter"), py::arg("key"));
+    // time: the frame time (a double: its bit pattern goes into the counter, so 0.0 and -0.0 differ)
+    m.def("noise_normal", [](uint64_t seed, double time, uint32_t pixel, uint32_t replica) {
+        uint64_t bits;
+        std::memcpy(&bits, &time, sizeof(bits));
+        return noise_normal(seed, bits, pixel, replica);
+    }, py::arg("seed"), py::arg("time"), py::arg("pixel"), py::arg("replica"));
+    m.def("noise_normals", [](uint64_t seed, double time,
+                              py::array_t<uint32_t, py::array::c_style | py::array::forcecast> pixels, uint32_t replica) {
+        uint64_t bits;
+        std::memcpy(&bits, &time, sizeof(bits));
+        py::array_t<double> z(pixels.size());
+        for (py::ssize_t i = 0; i < pixels.size(); ++i)
+            z.mutable_data()[i] = noise_normal(seed, bits, pixels.data()[i], replica);
+        return z;
+    }, py::arg("seed"), py::arg("time"), py::arg("pixels"), py::arg("replica"));
     m.def("fit_statistics", [](f64arr f, f64arr g, f64arr ell, double threshold, const std::vector<int64_t>& camera_pixels) {
         if (f.size() != g.size() || ell.size() != g.size()) throw py::value_error("f, g and ell must have one length");
         FitStats s;

@@ -78,6 +78,13 @@ void write_series_line(std::ostream& os, const MultiFrameEngine& mf, double read
         "batch", mf.batch_frames())("driver", "native").end();
 }
 
+void write_uncertainty_line(std::ostream& os, const UncertaintyLine& u) {
+    JsonLine j(os);
+    j("uncertainty", true)("replicas", u.replicas)("seed", u.seed)("noise_abs", u.noise_abs)(
+        "noise_shot", u.noise_shot)("noise_rel", u.noise_rel)("noise_kernel_ms", u.noise_kernel_ms)(
+        "moments_kernel_ms", u.moments_kernel_ms)("frames", u.frames).end();
+}
+
 void write_fit_line(std::ostream& os, uint64_t frames, uint64_t groups, double ms, const char* storage,
                     const char* format, int ranks) {
     JsonLine j(os);

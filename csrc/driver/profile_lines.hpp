@@ -86,6 +86,15 @@ void write_lead_line(std::ostream& os, const FrameId& f, const SolveInfo& info, 
 // a frame of a batch; warm_from: the composite frame whose iterate started it (-1: none)
 void write_batched_line(std::ostream& os, const FrameId& f, const SolveInfo& info, int batch, int64_t warm_from);
 void write_series_line(std::ostream& os, const MultiFrameEngine& mf, double reader_ms, double sink_ms);
+// --replicas: the noise definition's parameters and the total kernel times (device events) of the noise and moments
+// kernels over the run
+struct UncertaintyLine {
+    int replicas;
+    uint64_t seed;
+    double noise_abs, noise_shot, noise_rel, noise_kernel_ms, moments_kernel_ms;
+    uint64_t frames;
+};
+void write_uncertainty_line(std::ostream& os, const UncertaintyLine& u);
 void write_fit_line(std::ostream& os, uint64_t frames, uint64_t groups, double ms, const char* storage,
                     const char* format, int ranks);
 

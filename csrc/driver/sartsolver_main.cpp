@@ -19,9 +19,11 @@
 // frames solved together by the multi-frame MFMA engine; batches warm-start from the previous batch), --fit / --fit_only
 // (after the frames: fp64 fitted images and residuals of every stored solution into the output's /fit group),
 // --beta_scan B0,B1,... (every frame at each Laplacian weight as columns of the multi-frame engine; the L-curve into
-// the output's /beta_scan group, its corner's solution into /solution).
-// This file: main()'s sequence and the runs it starts (run_series, run_frames, run_fit_pass, run_scan). The shard and its
-// loaders: shard_load.{hpp,cpp}; the series' frame reader: frame_readahead.hpp; the --profile lines: profile_lines.
+// the output's /beta_scan group, its corner's solution into /solution), --replicas N (every frame and N noisy replicas
+// of it as columns of the multi-frame engine; per-voxel mean and spread into the output's /uncertainty group).
+// This file: main()'s sequence and the runs it starts (run_series, run_frames, run_fit_pass, run_scan,
+// run_replica_series). The shard and its loaders: shard_load.{hpp,cpp}; the series' frame reader:
+// frame_readahead.hpp; the --profile lines: profile_lines.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -31,12 +33,14 @@
 #include <limits>
 #include <map>
 #include <sstream>
+#include <tuple>
 #include <sys/prctl.h>
 #include <sys/stat.h>
 #include <unistd.h>
 
 #include <csignal>
 #include <cstdlib>
+#include <cstring>
 
 #include "../engine/comm.hpp"
 #include "../engine/engine64.hpp"
@@ -46,6 +50,7 @@
 #include "../native/fit.hpp"
 #include "../native/frames.hpp"
 #include "../native/lcurve.hpp"
+#include "../native/uncertainty.hpp"
 #include "frame_readahead.hpp"
 #include "profile_lines.hpp"
 #include "shard_load.hpp"
@@ -596,6 +601,205 @@ void run_scan_pass(Driver& d, const Shard& sh, const Csr& lap, const std::vector
                   << std::endl;
 }
 
+// A stream of its own with two events to time a kernel on it (--replicas: the noise and the moments kernels). What the
+// constructor has created is released when a later creation fails.
+struct TimedStream {
+    hipStream_t stream = nullptr;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    TimedStream() {
+        try {
+            hip_ok(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking), "hipStreamCreate");
+            hip_ok(hipEventCreate(&e0), "hipEventCreate");
+            hip_ok(hipEventCreate(&e1), "hipEventCreate");
+        } catch (...) {
+            release();
+            throw;
+        }
+    }
+    ~TimedStream() { release(); }
+    TimedStream(const TimedStream&) = delete;
+    TimedStream& operator=(const TimedStream&) = delete;
+    double elapsed_ms() const {  // between the two events, both reached
+        float ms = 0.f;
+        hip_ok(hipEventElapsedTime(&ms, e0, e1), "hipEventElapsedTime");
+        return ms;
+    }
+
+   private:
+    void release() {
+        if (e0) (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
+        if (stream) (void)hipStreamDestroy(stream);
+    }
+};
+
+// --replicas, the frame source's device side: the noisy replicas of this rank's pixels of a composite frame, generated
+// by csrc/kernels/noise.hip in chunks of up to kNoiseMaxChunk replicas on a stream of its own. A replica's bits are a
+// function of (seed, frame time, global pixel, replica): they depend neither on the chunk kept here nor on the thread or
+// the order of the requests. The last chunk stays on the host, one vector per replica, and a replica is handed over by
+// move (the series asks for a frame's replicas in order, each once; one asked for again is generated again).
+class ReplicaSource {
+   public:
+    ReplicaSource(const Driver& d, int64_t npix) : d_(d), cfg_(d.cfg), npix_(npix), ldo_((npix + 63) / 64 * 64) {
+        dg_.resize((size_t)ldo_);
+        dout_.resize((size_t)kNoiseMaxChunk * ldo_);
+        rows_.resize((size_t)kNoiseMaxChunk);
+    }
+    ReplicaSource(const ReplicaSource&) = delete;
+    ReplicaSource& operator=(const ReplicaSource&) = delete;
+    // replica r >= 1 of composite frame k (series index; g: its measured pixels of this rank, time: its time)
+    std::vector<double> replica(int64_t k, const std::vector<double>& g, double time, int r) {
+        if ((int64_t)g.size() != npix_) throw std::runtime_error("frame size does not match the shard's pixels");
+        const int r0 = 1 + (r - 1) / kNoiseMaxChunk * kNoiseMaxChunk;
+        if (k != frame_ || r0 != r0_ || rows_[r - r0].empty()) {
+            frame_ = -1;
+            const int n = std::min(kNoiseMaxChunk, cfg_.replicas - r0 + 1);
+            uint64_t bits;
+            static_assert(sizeof(bits) == sizeof(time), "the frame time's IEEE-754 bits");
+            std::memcpy(&bits, &time, sizeof(bits));
+            hip_ok(hipSetDevice(d_.device), "hipSetDevice");  // (the reader thread's first call)
+            hip_ok(hipMemcpyAsync(dg_.get(), g.data(), (size_t)npix_ * sizeof(double), hipMemcpyHostToDevice,
+                                  ts_.stream), "H2D frame");
+            hip_ok(hipEventRecord(ts_.e0, ts_.stream), "hipEventRecord");
+            launch_noise_replicas(dg_.get(), npix_, (uint64_t)d_.blk.offset, bits, (uint32_t)r0, n, cfg_.noise_abs,
+                                  cfg_.noise_shot, cfg_.noise_rel, cfg_.noise_seed, dout_.get(), ldo_, ts_.stream);
+            hip_ok(hipEventRecord(ts_.e1, ts_.stream), "hipEventRecord");
+            for (int i = 0; i < n; ++i) {  // every replica straight into the vector that is handed over
+                rows_[i].resize((size_t)npix_);
+                hip_ok(hipMemcpyAsync(rows_[i].data(), dout_.get() + (size_t)i * ldo_, (size_t)npix_ * sizeof(double),
+                                      hipMemcpyDeviceToHost, ts_.stream), "D2H replicas");
+            }
+            hip_ok(hipStreamSynchronize(ts_.stream), "noise replicas");
+            kernel_ms_ += ts_.elapsed_ms();
+            frame_ = k, r0_ = r0;
+        }
+        std::vector<double> out = std::move(rows_[r - r0_]);
+        rows_[r - r0_].clear();  // (a moved-from vector: empty by this line, whatever the library left)
+        return out;
+    }
+    double kernel_ms() const { return kernel_ms_; }
+
+   private:
+    const Driver& d_;
+    const Config& cfg_;
+    const int64_t npix_, ldo_;
+    DeviceArray<double> dg_, dout_;
+    std::vector<std::vector<double>> rows_;  // the chunk's replicas not handed over yet
+    TimedStream ts_;
+    int64_t frame_ = -1;
+    int r0_ = 0;
+    double kernel_ms_ = 0.0;
+};
+
+// --replicas: run_series over T (N + 1) virtual frames, virtual frame j = k (N + 1) + r being composite frame k's
+// replica r (r = 0: the measured frame itself), all cold columns of the multi-frame engine. Rank 0's sink keeps a
+// composite frame's columns on the host until the last one has arrived (no host collective in the sink, as in the scan),
+// takes the per-voxel moments of replicas 1 .. N (csrc/kernels/moments64.hip, on a stream of its own, synchronised
+// before the buffer is released), writes the frame's rows of /uncertainty and hands column 0 to the ordinary solution
+// writer in frame order.
+void run_replica_series(Driver& d, Solvers& s, const std::vector<uint64_t>& frames) {
+    const Config& cfg = d.cfg;
+    const CompositeImage& image = *d.image;
+    const int64_t N = cfg.replicas, nc = N + 1, T = (int64_t)frames.size(), nvirt = T * nc;
+    const int64_t nvoxel = (int64_t)d.in.nvoxel;
+    const size_t npix = (size_t)s.mf->nrows();
+    ReplicaSource noise(d, (int64_t)npix);
+    FrameReadahead ra(nvirt, 4 * (int64_t)cfg.batch_frames, [&](int64_t j) {
+        const int64_t k = j / nc;
+        std::vector<double> g = d.image->frame(frames[k]);  // (the image caches its frames)
+        if (j % nc == 0) return g;
+        return noise.replica(k, g, d.image->frame_time(frames[k]), (int)(j % nc));
+    });
+    auto src = [&](int64_t j, double* dst) {
+        const std::vector<double> f = ra.take(j);
+        if (f.size() != npix) throw std::runtime_error("frame size does not match the shard's pixels");
+        std::copy(f.begin(), f.end(), dst);
+    };
+    // rank 0: the columns of the composite frames in flight, the moments' device operands, the output
+    struct Columns {
+        std::vector<double> x;  // [nc][nvoxel]
+        std::vector<int32_t> status, iterations;
+        std::vector<uint8_t> use;  // [N]: replica r + 1 did not stop on a non-finite iterate
+        int64_t left;
+    };
+    std::map<int64_t, Columns> open;
+    // column 0 (with its status and update count) of the completed frames not written yet, by frame
+    std::map<int64_t, std::tuple<std::vector<double>, int32_t, int32_t>> done;
+    int64_t written = 0;
+    std::unique_ptr<UncertaintyWriter> file;
+    DeviceArray<double> dX, dmean, dstd;
+    DeviceArray<uint8_t> duse;
+    std::unique_ptr<TimedStream> ms;
+    std::vector<double> mean, sd;
+    if (d.rank == 0) {
+        const double triple[3] = {cfg.noise_abs, cfg.noise_shot, cfg.noise_rel};
+        file = std::make_unique<UncertaintyWriter>(cfg.output_file, (uint64_t)T, (uint64_t)N, (uint64_t)nvoxel, triple,
+                                                   cfg.noise_seed, cfg.replicas_keep);
+        dX.resize((size_t)N * nvoxel), dmean.resize((size_t)nvoxel), dstd.resize((size_t)nvoxel);
+        duse.resize((size_t)N);
+        mean.resize((size_t)nvoxel), sd.resize((size_t)nvoxel);
+        ms = std::make_unique<TimedStream>();
+    }
+    double sink_ms = 0.0, moments_ms = 0.0;
+    auto t_prev = Clock::now();
+    auto sink = [&](int64_t j, const double* xs, const SolveInfo& info) {
+        if (d.rank != 0) return;
+        const auto tsk = Clock::now();
+        const int64_t k = j / nc, r = j % nc;
+        auto it = open.find(k);
+        if (it == open.end())
+            it = open.emplace(k, Columns{std::vector<double>((size_t)nc * nvoxel), std::vector<int32_t>((size_t)nc),
+                                         std::vector<int32_t>((size_t)nc), std::vector<uint8_t>((size_t)N), nc}).first;
+        Columns& c = it->second;
+        std::copy(xs, xs + nvoxel, c.x.begin() + (size_t)r * nvoxel);
+        c.status[r] = info.status, c.iterations[r] = info.iterations;
+        if (r > 0) c.use[r - 1] = info.nonfinite ? 0 : 1;
+        if (info.nonfinite)
+            std::cerr << "warning: frame " << frames[k] << ", replica " << r << ": non-finite iterate, stopped"
+                      << std::endl;
+        if (--c.left == 0) {
+            hipStream_t mstream = ms->stream;
+            hip_ok(hipMemcpyAsync(dX.get(), c.x.data() + nvoxel, (size_t)N * nvoxel * sizeof(double),
+                                  hipMemcpyHostToDevice, mstream), "H2D replicas");
+            hip_ok(hipMemcpyAsync(duse.get(), c.use.data(), (size_t)N, hipMemcpyHostToDevice, mstream), "H2D mask");
+            hip_ok(hipEventRecord(ms->e0, mstream), "hipEventRecord");
+            launch_moments64(dX.get(), nvoxel, nvoxel, (int)N, duse.get(), dmean.get(), dstd.get(), mstream);
+            hip_ok(hipEventRecord(ms->e1, mstream), "hipEventRecord");
+            hip_ok(hipMemcpyAsync(mean.data(), dmean.get(), (size_t)nvoxel * sizeof(double), hipMemcpyDeviceToHost,
+                                  mstream), "D2H mean");
+            hip_ok(hipMemcpyAsync(sd.data(), dstd.get(), (size_t)nvoxel * sizeof(double), hipMemcpyDeviceToHost,
+                                  mstream), "D2H std");
+            hip_ok(hipStreamSynchronize(mstream), "moments");
+            moments_ms += ms->elapsed_ms();
+            const int32_t count = (int32_t)std::count(c.use.begin(), c.use.end(), (uint8_t)1);
+            file->write_frame((uint64_t)k, mean.data(), sd.data(), count, c.status.data(), c.iterations.data(),
+                              cfg.replicas_keep ? c.x.data() : nullptr);
+            c.x.resize((size_t)nvoxel);  // column 0 alone goes on to the solution writer
+            done.emplace(k, std::make_tuple(std::move(c.x), c.status[0], c.iterations[0]));
+            open.erase(it);
+            const auto now = Clock::now();
+            std::cout << "Processed in: " << std::chrono::duration<double, std::milli>(now - t_prev).count() << " ms"
+                      << std::endl;
+            t_prev = now;
+            // column 0 of the completed frames to /solution, in frame order (frames complete out of order)
+            for (auto dn = done.find(written); dn != done.end(); dn = done.find(written)) {
+                const uint64_t cur = frames[written];
+                d.writer->add(std::get<0>(dn->second), std::get<1>(dn->second), image.frame_time(cur),
+                              image.camera_frame_time(cur), std::get<2>(dn->second));
+                done.erase(dn);
+                ++written;
+            }
+        }
+        sink_ms += ms_since(tsk);
+    };
+    s.mf->solve_series(nvirt, src, sink, nullptr, false, nullptr);
+    if (d.rank == 0 && d.profile.is_open()) {
+        write_series_line(d.profile, *s.mf, ra.reader_ms(), sink_ms);
+        write_uncertainty_line(d.profile, {cfg.replicas, cfg.noise_seed, cfg.noise_abs, cfg.noise_shot, cfg.noise_rel,
+                                           noise.kernel_ms(), moments_ms, (uint64_t)T});
+    }
+}
+
 // GPU runs: this rank's device and the device communicator; --use_cpu: the host communicator alone
 void open_communicators(Driver& d) {
     if (d.gpu) {
@@ -646,10 +850,10 @@ void open_output(Driver& d, Resume& r) {
                 r.warm = stored.last_solution;
             }
         }
-        // --beta_scan: the scan creates the file with its /beta_scan group; /solution is added to it
+        // --beta_scan, --replicas: the run creates the file with its own group; /solution is added to it
         d.writer = std::make_unique<SolutionWriter>(cfg.output_file, d.in.camera_names, d.in.nvoxel,
                                                     (uint64_t)cfg.max_cached_solutions, r.appended,
-                                                    !cfg.beta_scan.empty());
+                                                    !cfg.beta_scan.empty() || cfg.replicas > 0);
         r.voxelgrid.read(d.in.rtm_files.begin()->second, "rtm/voxel_map");
         for (const auto& m : r.voxelgrid.warnings) std::cerr << "warning: " << m << std::endl;
     }
@@ -680,6 +884,8 @@ void run(Driver& d) {
     HostComm* host = d.host;
     const int rank = d.rank, size = d.size;
     d.cols = d.gpu && cfg.partition_voxels;
+    if (cfg.replicas > 0 && in.npixel >= (uint64_t)1 << 32)  // the noise counter takes the pixel index as 32 bits
+        throw Error("Argument replicas applies to fewer than 2^32 pixels, " + std::to_string(in.npixel) + " given.");
     d.vblk = d.cols ? block_partition(in.nvoxel, size, rank) : Block{0, in.nvoxel};
     d.blk = d.cols ? Block{0, in.npixel} : block_partition(in.npixel, size, rank);  // reference main.cpp:67-68
     if (d.blk.size == 0 || d.vblk.size == 0)
@@ -743,7 +949,9 @@ void run(Driver& d) {
         run_scan_series(d, solvers, frames, sc);
         solvers.reset();  // the engine's device buffers, before the pass allocates its own
         run_scan_pass(d, shard, lap, frames, sc);
-    } else if (batched)
+    } else if (cfg.replicas > 0)
+        run_replica_series(d, solvers, frames);
+    else if (batched)
         run_series(d, solvers, frames, res.warm);
     else
         run_frames(d, solvers, frames, res.warm);

@@ -151,6 +151,19 @@ void launch_fit64_csr(const SparseRtm& s, int64_t nrows, int64_t nvoxel, int64_t
 int64_t rough64_scratch_elems(int64_t n);
 void launch_rough64(const int64_t* row_ptr, const int32_t* col, const float* val, int64_t n, const double* X,
                     int64_t ldx, int nv, bool logx, double* eta2_out, double* scratch, hipStream_t stream);
+// noise.hip: replicas r0 .. r0 + nrep - 1 (nrep <= kNoiseMaxChunk per launch) of this rank's n pixels g (device fp64)
+// under the noise definition of philox.hpp, out[r - r0][p] with row stride ldo; replica 0 is g itself. pixel0: the
+// global index of g[0] (pixel0 + n <= 2^32); time_bits: the frame time's IEEE-754 bits. One thread per (pixel,
+// replica); padding beyond n is never written.
+constexpr int kNoiseMaxChunk = 64;
+void launch_noise_replicas(const double* g, int64_t n, uint64_t pixel0, uint64_t time_bits, uint32_t r0, int nrep,
+                           double abs_, double shot, double rel, uint64_t seed, double* out, int64_t ldo,
+                           hipStream_t stream);
+// moments64.hip: per-voxel mean and unbiased std over the rows r of X [n][ldx] (device fp64) with use[r] != 0, in index
+// order and two passes (mean, then deviations), one thread per voxel, no atomics; c rows used: std NaN for c < 2, mean
+// NaN for c = 0. Entries at and beyond nvoxel are neither read nor written.
+void launch_moments64(const double* X, int64_t ldx, int64_t nvoxel, int n, const uint8_t* use, double* mean,
+                      double* std_out, hipStream_t stream);
 // sart_update.hip
 void launch_prep_rows(const double* g, int64_t nrows, int64_t nrows_pad, double inv_s, const float* ray_length,
                       float len_thres, float* ghat, float* arow, float* gpos, float* wo, hipStream_t stream);

@@ -40,6 +40,16 @@ int to_int(const std::string& tok, const std::string& opt) {
     return (int)v;
 }
 
+uint64_t to_u64(const std::string& tok, const std::string& opt) {
+    const std::string t = trim(tok);
+    char* end = nullptr;
+    errno = 0;
+    const unsigned long long v = std::strtoull(t.c_str(), &end, 10);
+    if (t.empty() || t[0] == '-' || t[0] == '+' || end != t.c_str() + t.size() || errno == ERANGE)
+        throw Error("Failed to parse '" + tok + "' as an unsigned 64-bit integer for " + opt + ".");
+    return (uint64_t)v;
+}
+
 std::string fmt(double v) {
     std::ostringstream os;
     os << v;
@@ -142,12 +152,26 @@ std::string usage() {
            "                              -b only names the fallback weight (the nearest entry) when no corner is\n"
            "                              found. Not with --use_cpu, --fp64, --partition_voxels, --resume, --fit or\n"
            "                              --fit_only.\n"
+           "  --replicas N                Monte-Carlo error bars: solve every frame together with N (2 to 1024) noisy\n"
+           "                              replicas of it in one batched run: every replica is a column of the\n"
+           "                              multi-frame engine. Writes the per-voxel mean and standard deviation of the\n"
+           "                              replicas into the output file's /uncertainty group and the unperturbed\n"
+           "                              frame's solution into /solution. Needs a noise term; implies --no_guess and\n"
+           "                              --batch_frames >= 16. Not with --use_cpu, --fp64, --partition_voxels,\n"
+           "                              --resume, --fit, --fit_only or --beta_scan.\n"
+           "  --noise_abs A               With --replicas: noise floor in measurement units; per pixel\n"
+           "                              sigma^2 = A^2 + S g + (R g)^2. [default: 0]\n"
+           "  --noise_shot S              With --replicas: shot-noise coefficient in measurement units. [default: 0]\n"
+           "  --noise_rel R               With --replicas: relative noise. [default: 0]\n"
+           "  --noise_seed K              With --replicas: 64-bit seed of the noise (the noise depends on the seed, the\n"
+           "                              frame's time, the pixel and the replica alone). [default: 0]\n"
+           "  --replicas_keep             With --replicas: also store every replica's solution (/uncertainty/value).\n"
            "  --profile FILE              Write per-frame timing/iteration telemetry as JSON lines.\n";
 }
 
 Config parse_arguments(const std::vector<std::string>& argv) {
     Config c;
-    bool semantics_given = false, scan_given = false;
+    bool semantics_given = false, scan_given = false, replicas_given = false, noise_given = false;
     std::string scan_text;
     using Setter = std::function<void(const std::string&, const std::string&)>;
     std::map<std::string, Setter> valued = {
@@ -169,13 +193,18 @@ Config parse_arguments(const std::vector<std::string>& argv) {
         {"--rtm_format", [&](const std::string& v, const std::string&) { c.rtm_format = v; }},
         {"--fp64_semantics", [&](const std::string& v, const std::string&) { c.fp64_semantics = v; semantics_given = true; }},
         {"--beta_scan", [&](const std::string& v, const std::string&) { scan_text = v; scan_given = true; }},
+        {"--replicas", [&](const std::string& v, const std::string& o) { c.replicas = to_int(v, o); replicas_given = true; }},
+        {"--noise_abs", [&](const std::string& v, const std::string& o) { c.noise_abs = to_double(v, o); noise_given = true; }},
+        {"--noise_shot", [&](const std::string& v, const std::string& o) { c.noise_shot = to_double(v, o); noise_given = true; }},
+        {"--noise_rel", [&](const std::string& v, const std::string& o) { c.noise_rel = to_double(v, o); noise_given = true; }},
+        {"--noise_seed", [&](const std::string& v, const std::string& o) { c.noise_seed = to_u64(v, o); noise_given = true; }},
     };
     std::map<std::string, bool*> flags = {
         {"--logarithmic", &c.logarithmic}, {"--no_guess", &c.no_guess},   {"--use_cpu", &c.use_cpu},
         {"--parallel_read", &c.parallel_read}, {"--resume", &c.resume}, {"--two_pass", &c.two_pass},
         {"--partition_voxels", &c.partition_voxels}, {"--rtm_bf16", &c.rtm_bf16},
         {"--rtm_f16", &c.rtm_f16}, {"--rtm_f16_fused", &c.rtm_f16_fused}, {"--fp64", &c.fp64},
-        {"--fit", &c.fit}, {"--fit_only", &c.fit_only},
+        {"--fit", &c.fit}, {"--fit_only", &c.fit_only}, {"--replicas_keep", &c.replicas_keep},
     };
     const std::map<std::string, std::string> alias = {
         {"-o", "--output_file"},           {"-t", "--time_range"},          {"-w", "--wavelength_threshold"},
@@ -267,6 +296,27 @@ Config parse_arguments(const std::vector<std::string>& argv) {
         if (c.resume || c.fit || c.fit_only)
             throw Error("Argument beta_scan writes its own output: it cannot be combined with resume, fit or fit_only.");
         // every weight is a cold column of the batch engine: at least its narrowest batch, no lead engine, no chain
+        if (c.batch_frames == 1) c.batch_frames = 16;
+        c.no_guess = true;
+    }
+    if ((noise_given || c.replicas_keep) && !replicas_given)
+        throw Error("Arguments noise_abs, noise_shot, noise_rel, noise_seed and replicas_keep need replicas.");
+    if (replicas_given) {
+        if (c.replicas < 2 || c.replicas > 1024)
+            throw Error("Argument replicas must be within 2 .. 1024, " + std::to_string(c.replicas) + " given.");
+        const double noise[3] = {c.noise_abs, c.noise_shot, c.noise_rel};
+        const char* names[3] = {"noise_abs", "noise_shot", "noise_rel"};
+        for (int k = 0; k < 3; ++k)
+            if (!std::isfinite(noise[k]) || noise[k] < 0)
+                throw Error(std::string("Argument ") + names[k] + " must be finite and >= 0, " + fmt(noise[k]) + " given.");
+        if (!(c.noise_abs > 0 || c.noise_shot > 0 || c.noise_rel > 0))
+            throw Error("Argument replicas needs a noise term: one of noise_abs, noise_shot, noise_rel must be > 0.");
+        if (c.use_cpu || c.fp64 || c.partition_voxels)
+            throw Error("Argument replicas applies to the batched GPU solver with pixel-row shards only.");
+        if (c.resume || c.fit || c.fit_only || scan_given)
+            throw Error("Argument replicas writes its own output: it cannot be combined with resume, fit, fit_only or "
+                        "beta_scan.");
+        // every replica is a cold column of the batch engine, as a weight of the scan is
         if (c.batch_frames == 1) c.batch_frames = 16;
         c.no_guess = true;
     }

@@ -3,10 +3,12 @@
 // Same options, short aliases, defaults and validation as the reference CLI (reference
 // arguments.cpp:82-251, arguments.hpp:14-33), with an in-tree parser instead of p-ranav/argparse.
 // Extensions (not in the reference) are marked: --resume, --batch_frames, --two_pass, --partition_voxels,
-// --profile, --fp64, --fp64_semantics, --fit, --fit_only, --beta_scan.
+// --profile, --fp64, --fp64_semantics, --fit, --fit_only, --beta_scan, --replicas (with --noise_abs, --noise_shot,
+// --noise_rel, --noise_seed, --replicas_keep).
 #pragma once
 
 #include <array>
+#include <cstdint>
 #include <string>
 #include <vector>
 
@@ -51,7 +53,15 @@ struct Config {
     // in the output's /beta_scan group, its corner's solution in /solution. Implies batch_frames >= 16 and no_guess;
     // beta_laplace only names the fallback entry
     std::vector<double> beta_scan;
-    std::string profile_file;   // JSON timing/telemetry sidecar
+    // Monte-Carlo error bars: every frame's nominal column and `replicas` (2 .. 1024) noisy replicas of it in one
+    // batched run, per-voxel mean and spread into the output's /uncertainty group, the nominal column into /solution.
+    // Per pixel sigma^2 = noise_abs^2 + noise_shot g + (noise_rel g)^2 (README "Replicas"). Implies batch_frames >= 16
+    // and no_guess. 0: off
+    int replicas = 0;
+    double noise_abs = 0.0, noise_shot = 0.0, noise_rel = 0.0;
+    uint64_t noise_seed = 0;
+    bool replicas_keep = false;  // also store every replica's solution (/uncertainty/value)
+    std::string profile_file;  // JSON timing/telemetry sidecar
     bool help = false;
 };
 

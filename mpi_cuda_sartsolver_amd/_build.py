@@ -152,7 +152,7 @@ def build_native(verbose: bool = True) -> Path:
     objdir.mkdir(parents=True, exist_ok=True)
     LIBDIR.mkdir(parents=True, exist_ok=True)
     srcdir = CSRC / "native"
-    headers = sorted(srcdir.glob("*.hpp"))
+    headers = sorted(srcdir.glob("*.hpp")) + [CSRC / "kernels" / "philox.hpp"]  # (the host side of the noise definition)
     flags = ["-O3", "-std=c++17", "-fPIC", "-fopenmp", "-ffp-contract=off", "-Wall", "-Wno-sign-compare",
              *[f"-I{p}" for p in _py_includes()], f"-I{srcdir}"]
     libs = ["-fopenmp"]
