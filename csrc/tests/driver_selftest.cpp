@@ -1,15 +1,18 @@
 // Stand-alone self-test of the native driver's host-only units (built with sanitizers by
 // tests/test_driver_sanitizers.py): the bounded frame read-ahead (csrc/driver/frame_readahead.hpp) on a synthetic
-// source, and the --profile JSON-line builder (csrc/driver/profile_lines.hpp) against the operator<< chains it replaced.
+// source, the --profile JSON-line builder (csrc/driver/profile_lines.hpp) against the operator<< chains it replaced, and
+// the series runs' order rules (csrc/driver/series_order.hpp).
 #include <atomic>
 #include <cstdio>
 #include <cstdlib>
 #include <iostream>
+#include <memory>
 #include <sstream>
 #include <stdexcept>
 
 #include "../driver/frame_readahead.hpp"
 #include "../driver/profile_lines.hpp"
+#include "../driver/series_order.hpp"
 
 using namespace sart;
 
@@ -157,11 +160,82 @@ void test_json_line() {
     CHECK(e.str() == "{}\n");
 }
 
+void test_in_order() {
+    using Emitted = std::vector<int64_t>;
+    {  // first index 0, a move-only payload: puts 2, 0, 1, 4, 3 emit nothing; 0; 1, 2; nothing; 3, 4
+        InOrder<std::unique_ptr<int64_t>> q;
+        Emitted out;
+        auto emit = [&](int64_t k, std::unique_ptr<int64_t>&& item) {
+            const std::unique_ptr<int64_t> mine = std::move(item);  // moved out, not copied
+            CHECK(mine && *mine == 10 * k);
+            out.push_back(k);
+        };
+        q.drain(emit);  // nothing put yet
+        CHECK(out.empty() && q.empty());
+        const int64_t puts[] = {2, 0, 1, 4, 3};
+        const Emitted after[] = {{}, {0}, {0, 1, 2}, {0, 1, 2}, {0, 1, 2, 3, 4}};
+        for (int i = 0; i < 5; ++i) {
+            q.put(puts[i], std::make_unique<int64_t>(10 * puts[i]));
+            q.drain(emit);
+            CHECK(out == after[i]);
+            q.drain(emit);  // nothing ready: nothing more
+            CHECK(out == after[i]);
+            CHECK(q.empty() == (i == 2 || i == 4));
+        }
+    }
+    {  // first index 1 (the lead frame was written before the series): an item at 0 never leaves, 1 leaves at once
+        InOrder<int> q(1);
+        Emitted out;
+        auto emit = [&](int64_t k, int&& item) {
+            CHECK(item == (int)k + 100);
+            out.push_back(k);
+        };
+        q.put(0, 100);
+        q.drain(emit);
+        CHECK(out.empty() && !q.empty());
+        q.put(1, 101);
+        q.drain(emit);
+        CHECK(out == Emitted{1});
+        q.put(3, 103), q.put(2, 102);
+        q.drain(emit);
+        CHECK((out == Emitted{1, 2, 3}));
+        CHECK(!q.empty());  // (item 0 alone)
+    }
+}
+
+void test_column_count() {
+    {  // one column per frame: every arrival completes its frame
+        ColumnCount c(4, 1);
+        for (int64_t j : {2, 0, 3, 1}) {
+            CHECK(c.frame(j) == j && c.column(j) == 0);
+            CHECK(c.arrived(j));
+        }
+    }
+    {  // nc = 3, T = 2, arrivals interleaved across the frames: frame 1 completes at 5, frame 0 at 2, each once
+        ColumnCount c(2, 3);
+        std::vector<int64_t> completed;
+        for (int64_t j : {3, 0, 4, 1, 5, 2})
+            if (c.arrived(j)) completed.push_back(j);
+        CHECK((completed == std::vector<int64_t>{5, 2}));
+        CHECK(c.frame(5) == 1 && c.column(5) == 2 && c.frame(2) == 0 && c.column(2) == 2);
+    }
+    {  // T nc = 2^31 + 2: the last virtual index in 64-bit arithmetic
+        const int64_t nc = ((int64_t)1 << 30) + 1, T = 2, last = T * nc - 1;
+        CHECK(last == ((int64_t)1 << 31) + 1);
+        ColumnCount c(T, nc);
+        CHECK(c.frame(last) == 1 && c.column(last) == nc - 1);
+        CHECK(c.frame(nc) == 1 && c.column(nc) == 0 && c.frame(nc - 1) == 0 && c.column(nc - 1) == nc - 1);
+        CHECK(!c.arrived(last));
+    }
+}
+
 }  // namespace
 
 int main() {
     test_readahead();
     test_json_line();
+    test_in_order();
+    test_column_count();
     std::cout << "driver selftest OK" << std::endl;
     return 0;
 }
