@@ -934,6 +934,15 @@ PYBIND11_MODULE(_sart_hip, m) {
                                P<double>(std_out), S(stream));
     }, py::arg("X"), py::arg("ldx"), py::arg("nvoxel"), py::arg("n"), py::arg("use"), py::arg("mean"), py::arg("std"),
        py::arg("stream") = 0);
+    // ten doubles per column (sums [nv][10]) of nv <= 8 fp64 columns X [nv][ldx] against the truth t over nvoxel voxels;
+    // scratch: phantom64_scratch_elems(nvoxel) doubles
+    m.def("phantom64_scratch_elems", &sart::phantom64_scratch_elems, py::arg("nvoxel"));
+    m.def("phantom64", [](uintptr_t X, int64_t ldx, int64_t nvoxel, int nv, uintptr_t t, uintptr_t sums,
+                          uintptr_t scratch, uintptr_t stream) {
+        sart::launch_phantom64(P<const double>(X), ldx, nvoxel, nv, P<const double>(t), P<double>(sums),
+                               P<double>(scratch), S(stream));
+    }, py::arg("X"), py::arg("ldx"), py::arg("nvoxel"), py::arg("nv"), py::arg("t"), py::arg("sums"),
+       py::arg("scratch"), py::arg("stream") = 0);
     m.def("prep_rows", [](uintptr_t g, int64_t nrows, int64_t nrows_pad, double inv_s, uintptr_t ray_length,
                           float len_thres, uintptr_t ghat, uintptr_t arow, uintptr_t gpos, uintptr_t wo,
                           uintptr_t stream) {

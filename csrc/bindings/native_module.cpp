@@ -20,6 +20,7 @@
 #include "h5.hpp"
 #include "inputs.hpp"
 #include "lcurve.hpp"
+#include "phantom.hpp"
 #include "../kernels/philox.hpp"
 
 namespace py = pybind11;
@@ -93,6 +94,7 @@ PYBIND11_MODULE(_sart_native, m) {
         .def_readwrite("noise_rel", &Config::noise_rel)
         .def_readwrite("noise_seed", &Config::noise_seed)
         .def_readwrite("replicas_keep", &Config::replicas_keep)
+        .def_readwrite("phantom_file", &Config::phantom_file)
         .def_readwrite("profile_file", &Config::profile_file)
         .def_readwrite("help", &Config::help);
     m.def("parse_arguments", &parse_arguments, py::arg("argv"));
@@ -397,6 +399,56 @@ PYBIND11_MODULE(_sart_native, m) {
         return py::make_tuple(c.selected, c.found, py::array_t<double>(c.curvature.size(), c.curvature.data()));
     }, py::arg("rho"), py::arg("eta"), py::arg("ok"), py::arg("fallback"));
     // the noise definition of --replicas (kernels/philox.hpp: the text the noise kernel compiles)
+    // --phantom (phantom.hpp): the scores [..., 6] (kPhantomScoreNames' order) of sums [..., 10]
+    m.attr("phantom_score_names") = std::vector<std::string>(kPhantomScoreNames, kPhantomScoreNames + kPhantomScoreCount);
+    m.def("phantom_scores", [](f64arr sums) {
+        if (sums.ndim() < 1 || sums.shape(sums.ndim() - 1) != kPhantomSumCount)
+            throw std::invalid_argument("sums must be [..., 10]");
+        std::vector<py::ssize_t> shape(sums.shape(), sums.shape() + sums.ndim());
+        shape.back() = kPhantomScoreCount;
+        py::array_t<double> out(shape);
+        const py::ssize_t n = sums.size() / kPhantomSumCount;
+        for (py::ssize_t i = 0; i < n; ++i) {
+            const PhantomScores s = phantom_scores(sums.data() + i * kPhantomSumCount);
+            double* o = out.mutable_data() + i * kPhantomScoreCount;
+            o[0] = s.rel_l2, o[1] = s.cosine, o[2] = s.total_ratio, o[3] = s.peak_ratio, o[4] = s.max_error;
+            o[5] = s.inside_fraction;
+        }
+        return out;
+    }, py::arg("sums"));
+#ifdef SART_HAVE_HDF5
+    // (value [n, nvoxel], time [n]) of a validated phantom file
+    m.def("read_phantom_file", [](const std::string& path, uint64_t nvoxel) {
+        const PhantomFile f(path, nvoxel);
+        py::array_t<double> value({(py::ssize_t)f.count(), (py::ssize_t)nvoxel});
+        f.read_rows(0, f.count(), value.mutable_data());
+        return py::make_tuple(value, arr(f.times()));
+    }, py::arg("path"), py::arg("nvoxel"));
+    m.def("write_phantom_file", [](const std::string& path, f64arr value, py::object time, bool as_f32) {
+        if (value.ndim() != 2) throw std::invalid_argument("value must be [n, nvoxel]");
+        std::vector<double> t;
+        if (!time.is_none()) t = vec(time.cast<f64arr>());
+        if (!time.is_none() && (py::ssize_t)t.size() != value.shape(0))
+            throw std::invalid_argument("time must hold one entry per row of value");
+        write_phantom_file(path, value.data(), (uint64_t)value.shape(0), (uint64_t)value.shape(1),
+                           time.is_none() ? nullptr : t.data(), as_f32);
+    }, py::arg("path"), py::arg("value"), py::arg("time") = py::none(), py::arg("as_f32") = false);
+    py::class_<PhantomWriter>(m, "PhantomWriter")
+        .def(py::init([](const std::string& fn, uint64_t n, uint64_t nc, uint64_t npixel, const std::string& source,
+                         f64arr time, bool into_existing) {
+                 if ((uint64_t)time.size() != n) throw std::invalid_argument("time must hold one entry per phantom");
+                 return std::make_unique<PhantomWriter>(fn, n, nc, npixel, source, time.data(), into_existing);
+             }),
+             py::arg("filename"), py::arg("n"), py::arg("nc"), py::arg("npixel"), py::arg("source"), py::arg("time"),
+             py::arg("into_existing") = false)
+        .def("write_phantom", [](PhantomWriter& w, uint64_t k, f64arr sums, i32arr status, i32arr iterations) {
+            if (sums.ndim() != 2 || sums.shape(1) != kPhantomSumCount || status.size() != sums.shape(0) ||
+                iterations.size() != sums.shape(0))
+                throw std::invalid_argument("sums must be [nc, 10], status and iterations [nc]");
+            w.write_phantom(k, sums.data(), status.data(), iterations.data());
+        })
+        .def("write_images", [](PhantomWriter& w, f64arr image) { w.write_images(image.data()); });
+#endif
     m.def("philox4x32_10", [](const std::array<uint32_t, 4>& counter, const std::array<uint32_t, 2>& key) {
         const Philox4 o = philox4x32_10(counter[0], counter[1], counter[2], counter[3], key[0], key[1]);
         return py::make_tuple(o.w[0], o.w[1], o.w[2], o.w[3]);

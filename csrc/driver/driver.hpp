@@ -107,6 +107,8 @@ void run_frames(Driver& d, Solvers& s, const std::vector<uint64_t>& frames, std:
 void run_series(Driver& d, Solvers& s, const std::vector<uint64_t>& frames, const std::vector<double>& warm);
 void run_scan_series(Driver& d, Solvers& s, const std::vector<uint64_t>& frames, ScanColumns& sc);
 void run_replica_series(Driver& d, Solvers& s, const std::vector<uint64_t>& frames);
+// --phantom: the frames are projections of the phantom file's rows on this rank's shard; the number of phantoms
+uint64_t run_phantom_series(Driver& d, Solvers& s, const Shard& sh);
 // after the frames, main thread, collective; the engines released (their device buffers)
 void run_fit_pass(Driver& d, const Shard& sh);
 void run_scan_pass(Driver& d, const Shard& sh, const Csr& lap, const std::vector<uint64_t>& frames, ScanColumns& sc);

@@ -85,6 +85,12 @@ void write_uncertainty_line(std::ostream& os, const UncertaintyLine& u) {
         "moments_kernel_ms", u.moments_kernel_ms)("frames", u.frames).end();
 }
 
+void write_phantom_line(std::ostream& os, const PhantomLine& p) {
+    JsonLine j(os);
+    j("phantom", true)("phantoms", p.phantoms)("replicas", p.replicas)("groups", p.groups)(
+        "projection_kernel_ms", p.projection_kernel_ms)("scoring_kernel_ms", p.scoring_kernel_ms).end();
+}
+
 void write_fit_line(std::ostream& os, uint64_t frames, uint64_t groups, double ms, const char* storage,
                     const char* format, int ranks) {
     JsonLine j(os);

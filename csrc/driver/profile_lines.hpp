@@ -95,6 +95,14 @@ struct UncertaintyLine {
     uint64_t frames;
 };
 void write_uncertainty_line(std::ostream& os, const UncertaintyLine& u);
+// --phantom: the counts and the total kernel times (device events) of the projection and scoring kernels over the run
+struct PhantomLine {
+    uint64_t phantoms;
+    int replicas;
+    uint64_t groups;  // projection passes over the shard
+    double projection_kernel_ms, scoring_kernel_ms;
+};
+void write_phantom_line(std::ostream& os, const PhantomLine& p);
 void write_fit_line(std::ostream& os, uint64_t frames, uint64_t groups, double ms, const char* storage,
                     const char* format, int ranks);
 

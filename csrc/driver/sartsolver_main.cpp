@@ -20,9 +20,11 @@
 // (after the frames: fp64 fitted images and residuals of every stored solution into the output's /fit group),
 // --beta_scan B0,B1,... (every frame at each Laplacian weight as columns of the multi-frame engine; the L-curve into
 // the output's /beta_scan group, its corner's solution into /solution), --replicas N (every frame and N noisy replicas
-// of it as columns of the multi-frame engine; per-voxel mean and spread into the output's /uncertainty group).
+// of it as columns of the multi-frame engine; per-voxel mean and spread into the output's /uncertainty group),
+// --phantom FILE (the frames solved are the fp64 projections of known emissivities through the shard; every column
+// scored against its truth into the output's /phantom group).
 // This file: main()'s sequence up to the runs it starts (driver.hpp). The frame loops: series_runs.cpp (frame by frame,
-// --batch_frames) and column_runs.cpp (--beta_scan, --replicas), on the series skeleton of driver.hpp with the order
+// --batch_frames) and column_runs.cpp (--beta_scan, --replicas, --phantom), on the series skeleton of driver.hpp with the order
 // rules of series_order.hpp and the frame reader of frame_readahead.hpp; the passes after the frames: fit_pass.cpp. The
 // shard and its loaders: shard_load.{hpp,cpp}; the --profile lines: profile_lines.
 #include <sys/prctl.h>
@@ -161,10 +163,11 @@ void open_output(Driver& d, Resume& r) {
                 r.warm = stored.last_solution;
             }
         }
-        // --beta_scan, --replicas: the run creates the file with its own group; /solution is added to it
+        // --beta_scan, --replicas, --phantom: the run creates the file with its own group; /solution is added to it
         d.writer = std::make_unique<SolutionWriter>(cfg.output_file, d.in.camera_names, d.in.nvoxel,
                                                     (uint64_t)cfg.max_cached_solutions, r.appended,
-                                                    !cfg.beta_scan.empty() || cfg.replicas > 0);
+                                                    !cfg.beta_scan.empty() || cfg.replicas > 0 ||
+                                                        !cfg.phantom_file.empty());
         r.voxelgrid.read(d.in.rtm_files.begin()->second, "rtm/voxel_map");
         for (const auto& m : r.voxelgrid.warnings) std::cerr << "warning: " << m << std::endl;
     }
@@ -249,7 +252,9 @@ void run(Driver& d) {
     for (uint64_t i = 0; i < d.image->nframe(); ++i)
         if (solve && d.image->frame_time(i) > res.skip_until + 1e-12) frames.push_back(i);
     const auto t_loop = Clock::now();
-    if (!cfg.beta_scan.empty()) {
+    if (!cfg.phantom_file.empty()) {  // the phantoms stand in for the measured frames (in the closing line too)
+        frames.assign((size_t)run_phantom_series(d, solvers, shard), 0);
+    } else if (!cfg.beta_scan.empty()) {
         ScanColumns sc;
         if (rank == 0) {
             const size_t nvirt = frames.size() * cfg.beta_scan.size();

@@ -164,6 +164,15 @@ void launch_noise_replicas(const double* g, int64_t n, uint64_t pixel0, uint64_t
 // NaN for c = 0. Entries at and beyond nvoxel are neither read nor written.
 void launch_moments64(const double* X, int64_t ldx, int64_t nvoxel, int n, const uint8_t* use, double* mean,
                       double* std_out, hipStream_t stream);
+// phantom64.hip: nv <= 8 fp64 columns X [nv][ldx] scored against one truth t over the voxels v < nvoxel, ten doubles
+// per column into sums_out [nv][kPhantomSums] (device): sum t, sum x, sum t^2, sum x^2, sum x t, sum (x - t)^2, sum of x
+// over the voxels with t > 0, max |x - t|, max t, max x. Plain fp64 products and additions (no contraction), per-block
+// partials into scratch (phantom64_scratch_elems(nvoxel) doubles), then a fixed-order second stage: no atomics, a
+// column's ten values depend on X[j] and t alone. Entries at and beyond nvoxel are not read. nvoxel >= 1.
+constexpr int kPhantomSums = 10;
+int64_t phantom64_scratch_elems(int64_t nvoxel);
+void launch_phantom64(const double* X, int64_t ldx, int64_t nvoxel, int nv, const double* t, double* sums_out,
+                      double* scratch, hipStream_t stream);
 // sart_update.hip
 void launch_prep_rows(const double* g, int64_t nrows, int64_t nrows_pad, double inv_s, const float* ray_length,
                       float len_thres, float* ghat, float* arow, float* gpos, float* wo, hipStream_t stream);

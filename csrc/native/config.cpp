@@ -166,12 +166,23 @@ std::string usage() {
            "  --noise_seed K              With --replicas: 64-bit seed of the noise (the noise depends on the seed, the\n"
            "                              frame's time, the pixel and the replica alone). [default: 0]\n"
            "  --replicas_keep             With --replicas: also store every replica's solution (/uncertainty/value).\n"
+           "  --phantom FILE              Reconstruct known emissivities: the frames solved are the fp64 projections of\n"
+           "                              the rows of FILE's /phantom/value ([n][nvoxel], >= 0) through the RTM as\n"
+           "                              stored, not the measured frames. The RTM and image files are given and\n"
+           "                              validated as in any run (they fix the cameras and pixels); the images'\n"
+           "                              frames and -t / --time_range are not used. Every column is scored against\n"
+           "                              its truth into the output file's /phantom group; the noise-free column goes\n"
+           "                              to /solution. With --replicas N and the --noise_* flags every phantom also\n"
+           "                              gets N noisy replicas. Implies --no_guess and --batch_frames >= 16. Not with\n"
+           "                              --use_cpu, --batch_frames 1, --fp64, --partition_voxels, --resume, --fit,\n"
+           "                              --fit_only or --beta_scan.\n"
            "  --profile FILE              Write per-frame timing/iteration telemetry as JSON lines.\n";
 }
 
 Config parse_arguments(const std::vector<std::string>& argv) {
     Config c;
     bool semantics_given = false, scan_given = false, replicas_given = false, noise_given = false;
+    bool batch_given = false, phantom_given = false;
     std::string scan_text;
     using Setter = std::function<void(const std::string&, const std::string&)>;
     std::map<std::string, Setter> valued = {
@@ -188,7 +199,7 @@ Config parse_arguments(const std::vector<std::string>& argv) {
         {"--raytransfer_name", [&](const std::string& v, const std::string&) { c.raytransfer_name = v; }},
         {"--max_cached_frames", [&](const std::string& v, const std::string& o) { c.max_cached_frames = to_int(v, o); }},
         {"--max_cached_solutions", [&](const std::string& v, const std::string& o) { c.max_cached_solutions = to_int(v, o); }},
-        {"--batch_frames", [&](const std::string& v, const std::string& o) { c.batch_frames = to_int(v, o); }},
+        {"--batch_frames", [&](const std::string& v, const std::string& o) { c.batch_frames = to_int(v, o); batch_given = true; }},
         {"--profile", [&](const std::string& v, const std::string&) { c.profile_file = v; }},
         {"--rtm_format", [&](const std::string& v, const std::string&) { c.rtm_format = v; }},
         {"--fp64_semantics", [&](const std::string& v, const std::string&) { c.fp64_semantics = v; semantics_given = true; }},
@@ -198,6 +209,7 @@ Config parse_arguments(const std::vector<std::string>& argv) {
         {"--noise_shot", [&](const std::string& v, const std::string& o) { c.noise_shot = to_double(v, o); noise_given = true; }},
         {"--noise_rel", [&](const std::string& v, const std::string& o) { c.noise_rel = to_double(v, o); noise_given = true; }},
         {"--noise_seed", [&](const std::string& v, const std::string& o) { c.noise_seed = to_u64(v, o); noise_given = true; }},
+        {"--phantom", [&](const std::string& v, const std::string&) { c.phantom_file = v; phantom_given = true; }},
     };
     std::map<std::string, bool*> flags = {
         {"--logarithmic", &c.logarithmic}, {"--no_guess", &c.no_guess},   {"--use_cpu", &c.use_cpu},
@@ -245,6 +257,7 @@ Config parse_arguments(const std::vector<std::string>& argv) {
         }
     }
     for (; i < argv.size(); ++i) c.input_files.push_back(argv[i]);
+    const bool batch_one = batch_given && c.batch_frames == 1;  // asked for by name (the default of 1 may be raised)
 
     // validation (reference arguments.cpp:184-248)
     if (c.ray_density_threshold < 0)
@@ -317,6 +330,17 @@ Config parse_arguments(const std::vector<std::string>& argv) {
             throw Error("Argument replicas writes its own output: it cannot be combined with resume, fit, fit_only or "
                         "beta_scan.");
         // every replica is a cold column of the batch engine, as a weight of the scan is
+        if (c.batch_frames == 1) c.batch_frames = 16;
+        c.no_guess = true;
+    }
+    if (phantom_given) {
+        if (c.phantom_file.empty()) throw Error("Argument phantom needs a file name.");
+        if (c.use_cpu || c.fp64 || c.partition_voxels || batch_one)
+            throw Error("Argument phantom applies to the batched GPU solver with pixel-row shards only.");
+        if (c.resume || c.fit || c.fit_only || scan_given)
+            throw Error("Argument phantom writes its own output: it cannot be combined with resume, fit, fit_only or "
+                        "beta_scan.");
+        // every phantom (and every replica of it) is a cold column of the batch engine, as a weight of the scan is
         if (c.batch_frames == 1) c.batch_frames = 16;
         c.no_guess = true;
     }

@@ -4,7 +4,7 @@
 // arguments.cpp:82-251, arguments.hpp:14-33), with an in-tree parser instead of p-ranav/argparse.
 // Extensions (not in the reference) are marked: --resume, --batch_frames, --two_pass, --partition_voxels,
 // --profile, --fp64, --fp64_semantics, --fit, --fit_only, --beta_scan, --replicas (with --noise_abs, --noise_shot,
-// --noise_rel, --noise_seed, --replicas_keep).
+// --noise_rel, --noise_seed, --replicas_keep), --phantom.
 #pragma once
 
 #include <array>
@@ -61,6 +61,10 @@ struct Config {
     double noise_abs = 0.0, noise_shot = 0.0, noise_rel = 0.0;
     uint64_t noise_seed = 0;
     bool replicas_keep = false;  // also store every replica's solution (/uncertainty/value)
+    // Reconstruct known emissivities: the frames solved are the fp64 projections of the rows of this file's
+    // /phantom/value through the RTM as stored (with `replicas`: and noisy replicas of them), scored against their truth
+    // into the output's /phantom group, column 0 into /solution. Implies batch_frames >= 16 and no_guess. Empty: off
+    std::string phantom_file;
     std::string profile_file;  // JSON timing/telemetry sidecar
     bool help = false;
 };

@@ -124,3 +124,17 @@ def make_case(directory: str, cameras=("cam_a", "cam_b"), shapes=((6, 8), (5, 7)
     files = rtm_files + image_files
     return Case(files=files, rtm_files=rtm_files, image_files=image_files, laplacian_file=lap, A=A, times=times,
                 frames=frames, phantoms=phantoms, npixel=A.shape[0], nvoxel=nvoxel, grid=grid, masks=masks)
+
+
+def write_phantom_file(path: str, value, time=None, dtype=np.float64) -> str:
+    """A phantom file for ``--phantom`` (docs/FORMATS.md): ``/phantom/value`` ``[n, nvoxel]`` stored as ``dtype``
+    (float32 or float64) and, unless None, ``/phantom/time`` ``[n]``. Nothing is validated here: the reader's refusals
+    are tested with files this writes."""
+    v = np.ascontiguousarray(np.asarray(value, dtype=np.float64))
+    if v.ndim != 2:
+        raise ValueError("value must be [n, nvoxel]")
+    if np.dtype(dtype) not in (np.dtype(np.float32), np.dtype(np.float64)):
+        raise ValueError("dtype must be float32 or float64")
+    t = None if time is None else np.ascontiguousarray(np.asarray(time, dtype=np.float64).reshape(-1))
+    native().write_phantom_file(path, v, t, np.dtype(dtype) == np.dtype(np.float32))
+    return path
