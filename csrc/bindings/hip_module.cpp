@@ -943,6 +943,16 @@ PYBIND11_MODULE(_sart_hip, m) {
                                P<double>(scratch), S(stream));
     }, py::arg("X"), py::arg("ldx"), py::arg("nvoxel"), py::arg("nv"), py::arg("t"), py::arg("sums"),
        py::arg("scratch"), py::arg("stream") = 0);
+    // hold-out sums (sums [n][ncam][6]) of n fp64 fitted images F [n][ldf] against the frame g: the pixels of camera m
+    // are cam_start[m] .. cam_start[m + 1] - 1 (int64 [ncam + 1]), fold int32 per pixel, held int32 [n] (-1: none);
+    // ldf >= cam_start[ncam] is the caller's to keep
+    m.def("holdout64", [](uintptr_t F, int64_t ldf, int n, uintptr_t g, uintptr_t ell, double threshold, uintptr_t fold,
+                          uintptr_t held, uintptr_t cam_start, int ncam, uintptr_t sums, uintptr_t stream) {
+        sart::launch_holdout64(P<const double>(F), ldf, n, P<const double>(g), P<const double>(ell), threshold,
+                               P<const int32_t>(fold), P<const int32_t>(held), P<const int64_t>(cam_start), ncam,
+                               P<double>(sums), S(stream));
+    }, py::arg("F"), py::arg("ldf"), py::arg("n"), py::arg("g"), py::arg("ell"), py::arg("threshold"), py::arg("fold"),
+       py::arg("held"), py::arg("cam_start"), py::arg("ncam"), py::arg("sums"), py::arg("stream") = 0);
     m.def("prep_rows", [](uintptr_t g, int64_t nrows, int64_t nrows_pad, double inv_s, uintptr_t ray_length,
                           float len_thres, uintptr_t ghat, uintptr_t arow, uintptr_t gpos, uintptr_t wo,
                           uintptr_t stream) {

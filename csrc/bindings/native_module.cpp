@@ -18,6 +18,7 @@
 #include "fixtures.hpp"
 #include "frames.hpp"
 #include "h5.hpp"
+#include "holdout.hpp"
 #include "inputs.hpp"
 #include "lcurve.hpp"
 #include "phantom.hpp"
@@ -95,6 +96,10 @@ PYBIND11_MODULE(_sart_native, m) {
         .def_readwrite("noise_seed", &Config::noise_seed)
         .def_readwrite("replicas_keep", &Config::replicas_keep)
         .def_readwrite("phantom_file", &Config::phantom_file)
+        .def_readwrite("holdout", &Config::holdout)
+        .def_readwrite("holdout_cameras", &Config::holdout_cameras)
+        .def_readwrite("holdout_seed", &Config::holdout_seed)
+        .def_readwrite("holdout_betas", &Config::holdout_betas)
         .def_readwrite("profile_file", &Config::profile_file)
         .def_readwrite("help", &Config::help);
     m.def("parse_arguments", &parse_arguments, py::arg("argv"));
@@ -265,6 +270,20 @@ PYBIND11_MODULE(_sart_native, m) {
         return py::array_t<double>();
 #endif
     });
+#ifdef SART_HAVE_HDF5
+    // a scalar fixed-length string dataset (/holdout/mode)
+    m.def("read_dataset_string", [](const std::string& fn, const std::string& name) {
+        SART_H5_LOCK;
+        H5Id f = h5_open_file(fn);
+        H5Id d = h5_open_dataset(f, name);
+        H5Id t(H5Dget_type(d), H5Id::kType);
+        if (H5Tget_class(t) != H5T_STRING || H5Tis_variable_str(t) > 0 || !h5_dims(d).empty())
+            throw Error("dataset " + name + " is not a scalar fixed-length string");
+        std::string text(H5Tget_size(t), '\0');
+        if (H5Dread(d, t, H5S_ALL, H5S_ALL, H5P_DEFAULT, text.data()) < 0) throw Error("Unable to read " + name + ".");
+        return text.substr(0, text.find('\0'));
+    });
+#endif
     // a dataset's stored type as a NumPy type string ("<f8", "<i4", "|u1", ...; tests of the file formats)
     m.def("dataset_dtype", [](const std::string& fn, const std::string& name) {
 #ifdef SART_HAVE_HDF5
@@ -399,6 +418,44 @@ PYBIND11_MODULE(_sart_native, m) {
         return py::make_tuple(c.selected, c.found, py::array_t<double>(c.curvature.size(), c.curvature.data()));
     }, py::arg("rho"), py::arg("eta"), py::arg("ok"), py::arg("fallback"));
     // the noise definition of --replicas (kernels/philox.hpp: the text the noise kernel compiles)
+    // --holdout (holdout.hpp): the folds of the global pixels pixel0 .. pixel0 + n - 1 (camera_pixels given: camera mode)
+    m.def("holdout_folds", [](uint64_t n, int K, uint64_t seed, uint64_t pixel0, py::object camera_pixels) {
+        py::array_t<int32_t> out((py::ssize_t)n);
+        if (camera_pixels.is_none()) {
+            holdout_pixel_folds(seed, K, pixel0, n, out.mutable_data());
+        } else {
+            const std::vector<int64_t> cams = camera_pixels.cast<std::vector<int64_t>>();
+            holdout_camera_folds(cams.data(), (int)cams.size(), pixel0, n, out.mutable_data());
+        }
+        return out;
+    }, py::arg("n"), py::arg("K") = 0, py::arg("seed") = 0, py::arg("pixel0") = 0, py::arg("camera_pixels") = py::none());
+    m.def("holdout_mask", [](f64arr g, i32arr fold, int held) {
+        if (g.ndim() != 1 || fold.ndim() != 1 || g.size() != fold.size())
+            throw std::invalid_argument("g and fold must be [npixel]");
+        py::array_t<double> out(g.size());
+        holdout_mask(g.data(), fold.data(), (int64_t)g.size(), held, out.mutable_data());
+        return out;
+    }, py::arg("g"), py::arg("fold"), py::arg("held"));
+    m.def("holdout_fallback", [](f64arr betas, double beta) {
+        if (betas.size() < 1) throw std::invalid_argument("betas must hold at least one weight");
+        return holdout_fallback(betas.data(), (int)betas.size(), beta);
+    }, py::arg("betas"), py::arg("beta"));
+    // one composite frame: sums [nb, K + 1, ncam, 6], ok [nb, K + 1] -> (cv_error [nb], cv_relative [nb], train_error [nb],
+    // cv_error_camera [nb, ncam], eligible [nb], selected, found)
+    m.def("holdout_scores", [](f64arr sums, u8arr ok, int fallback) {
+        if (sums.ndim() != 4 || sums.shape(3) != kHoldoutSumCount || sums.shape(0) < 1 || sums.shape(1) < 2 ||
+            sums.shape(2) < 1)
+            throw std::invalid_argument("sums must be [nb, K + 1, ncam, 6]");
+        if (ok.ndim() != 2 || ok.shape(0) != sums.shape(0) || ok.shape(1) != sums.shape(1))
+            throw std::invalid_argument("ok must be [nb, K + 1]");
+        const int nb = (int)sums.shape(0), K = (int)sums.shape(1) - 1, ncam = (int)sums.shape(2);
+        if (fallback < 0 || fallback >= nb) throw std::invalid_argument("fallback must name a ladder entry");
+        const HoldoutScores s = holdout_scores(sums.data(), ok.data(), nb, K, ncam, fallback);
+        py::array_t<double> cam({(py::ssize_t)nb, (py::ssize_t)ncam});
+        std::copy(s.cv_error_camera.begin(), s.cv_error_camera.end(), cam.mutable_data());
+        return py::make_tuple(arr(s.cv_error), arr(s.cv_relative), arr(s.train_error), cam, arr(s.eligible),
+                              (int)s.selected, (int)s.found);
+    }, py::arg("sums"), py::arg("ok"), py::arg("fallback"));
     // --phantom (phantom.hpp): the scores [..., 6] (kPhantomScoreNames' order) of sums [..., 10]
     m.attr("phantom_score_names") = std::vector<std::string>(kPhantomScoreNames, kPhantomScoreNames + kPhantomScoreCount);
     m.def("phantom_scores", [](f64arr sums) {

@@ -1,7 +1,8 @@
 // The native driver's series of virtual frames (SeriesRun over T nc columns, virtual frame j = k nc + c being column c
 // of composite frame k, all cold columns of the multi-frame engine): --beta_scan (run_scan_series), --replicas
 // (run_replica_series with its noise source) and --phantom (run_phantom_series with its projection source), the last
-// two on one loop (run_replica_columns).
+// two on one loop (run_replica_columns), and --holdout (run_holdout_series: T nb (K + 1) columns, masked on the reader
+// thread).
 #include <cstring>
 #include <functional>
 
@@ -316,6 +317,38 @@ void run_scan_series(Driver& d, Solvers& s, const std::vector<uint64_t>& frames,
         if (cols.arrived(j)) run.tick();
     });
     if (d.rank == 0) sc.file->close();
+}
+
+// --holdout, the frame loop: virtual frame j = (k nb + i) (K + 1) + c is composite frame k at weight i, as measured
+// (c = 0) or with the pixels of fold c - 1 set to the solver's exclusion marker (reader thread: one pass over this rank's
+// pixels, the fold of global pixel blk.offset + p). Rank 0 writes every finished column into /holdout as it arrives;
+// nothing goes to /solution yet.
+void run_holdout_series(Driver& d, Solvers& s, const std::vector<uint64_t>& frames, HoldoutColumns& hc) {
+    const int64_t nb = hc.nb(), nc = hc.K + 1, T = (int64_t)frames.size(), nvirt = T * nb * nc;
+    ColumnCount cols(T, nb * nc);
+    const int32_t* fold = hc.folds.data() + d.blk.offset;
+    SeriesRun run(d, *s.mf, nvirt, [&](int64_t j) {
+        std::vector<double> g = d.image->frame(frames[cols.frame(j)]);  // (the image caches its frames)
+        const int c = (int)(cols.column(j) % nc);
+        if (c > 0) holdout_mask(g.data(), fold, (int64_t)g.size(), c - 1, g.data());
+        return g;
+    });
+    std::vector<float> frame_beta;
+    if (!d.cfg.holdout_betas.empty()) {
+        frame_beta.resize((size_t)nvirt);
+        for (int64_t j = 0; j < nvirt; ++j) frame_beta[j] = (float)hc.betas[cols.column(j) / nc];
+    }
+    run.solve(0, nullptr, false, frame_beta.empty() ? nullptr : frame_beta.data(),
+              [&](int64_t j, const double* xs, const SolveInfo& info) {
+        const int64_t k = cols.frame(j), i = cols.column(j) / nc, c = cols.column(j) % nc;
+        hc.file->write_column((uint64_t)k, (uint64_t)i, (uint64_t)c, xs, info.status, info.iterations);
+        hc.status[j] = info.status, hc.iterations[j] = info.iterations, hc.ok[j] = info.nonfinite ? 0 : 1;
+        if (info.nonfinite)
+            std::cerr << "warning: frame " << frames[k] << ", beta " << hc.betas[i] << ", hold-out column " << c
+                      << ": non-finite iterate, stopped" << std::endl;
+        if (cols.arrived(j)) run.tick();
+    });
+    if (d.rank == 0) hc.file->close();
 }
 
 // --replicas: the composite frames are the measured ones (run_replica_columns)

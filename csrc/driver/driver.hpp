@@ -10,6 +10,7 @@
 #include "../engine/multiframe.hpp"
 #include "../native/cpu_solver.hpp"
 #include "../native/frames.hpp"
+#include "../native/holdout.hpp"
 #include "../native/lcurve.hpp"
 #include "frame_readahead.hpp"
 #include "profile_lines.hpp"
@@ -102,15 +103,31 @@ struct ScanColumns {
     std::vector<uint8_t> ok;                  // [T nb], rank 0: the column did not stop on a non-finite iterate
 };
 
+// --holdout: what the run shares between the series and the hold-out pass. K, the fold table over all pixels and the
+// cameras' pixel ranges are the same on every rank; the columns' solutions are in the file
+struct HoldoutColumns {
+    int K = 0;                                // folds: --holdout K, or the number of cameras
+    std::vector<double> betas;                // [nb]: --holdout_betas, or -b alone
+    std::vector<int32_t> folds;               // [npixel]
+    std::vector<int64_t> cam_start;           // [ncam + 1]
+    std::unique_ptr<HoldoutWriter> file;      // rank 0
+    std::vector<int32_t> status, iterations;  // [T nb (K + 1)], rank 0
+    std::vector<uint8_t> ok;                  // [T nb (K + 1)], rank 0: the column did not stop on a non-finite iterate
+    int64_t nb() const { return (int64_t)betas.size(); }
+    int64_t ncam() const { return (int64_t)cam_start.size() - 1; }
+};
+
 // frames: the composite frames to solve; warm: the resumed solution (all voxels) or empty
 void run_frames(Driver& d, Solvers& s, const std::vector<uint64_t>& frames, std::vector<double> warm);
 void run_series(Driver& d, Solvers& s, const std::vector<uint64_t>& frames, const std::vector<double>& warm);
 void run_scan_series(Driver& d, Solvers& s, const std::vector<uint64_t>& frames, ScanColumns& sc);
 void run_replica_series(Driver& d, Solvers& s, const std::vector<uint64_t>& frames);
+void run_holdout_series(Driver& d, Solvers& s, const std::vector<uint64_t>& frames, HoldoutColumns& hc);
 // --phantom: the frames are projections of the phantom file's rows on this rank's shard; the number of phantoms
 uint64_t run_phantom_series(Driver& d, Solvers& s, const Shard& sh);
 // after the frames, main thread, collective; the engines released (their device buffers)
 void run_fit_pass(Driver& d, const Shard& sh);
 void run_scan_pass(Driver& d, const Shard& sh, const Csr& lap, const std::vector<uint64_t>& frames, ScanColumns& sc);
+void run_holdout_pass(Driver& d, const Shard& sh, const std::vector<uint64_t>& frames, HoldoutColumns& hc);
 
 }  // namespace sart

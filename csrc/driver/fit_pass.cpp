@@ -1,5 +1,6 @@
 // The native driver's passes after the frames (main thread, collective): groups of rows of the output file projected in
-// fp64 on every rank's shard (FitProjector) for --fit / --fit_only (run_fit_pass) and --beta_scan (run_scan_pass).
+// fp64 on every rank's shard (FitProjector) for --fit / --fit_only (run_fit_pass), --beta_scan (run_scan_pass) and
+// --holdout (run_holdout_pass).
 #include <cmath>
 #include <sstream>
 
@@ -245,6 +246,98 @@ void run_scan_pass(Driver& d, const Shard& sh, const Csr& lap, const std::vector
     if (d.rank == 0)
         std::cout << "Beta scan of " << T << " frame(s) x " << nb << " weights in: " << ms_since(t_scan) << " ms"
                   << std::endl;
+}
+
+// --holdout, after the loop: the rows of /holdout/value through FitProjector::for_groups -- rank 0 uploads the group's
+// images next to the frame's measured pixels, the ray lengths and the fold table and takes the six sums per column and
+// camera (csrc/kernels/holdout64.hip; a group that straddles two composite frames is scored in two launches). The
+// images are the zero-filled host all-reduce's and a value of the kernel depends on its column and camera alone, so
+// /holdout depends neither on the rank count (given the same columns) nor on the grouping. A frame whose nb (K + 1)
+// columns are complete gets its scores (holdout_scores); column 0 of the selected weight goes to /solution through the
+// ordinary writer, in frame order.
+void run_holdout_pass(Driver& d, const Shard& sh, const std::vector<uint64_t>& frames, HoldoutColumns& hc) {
+    const Config& cfg = d.cfg;
+    const CompositeImage& image = *d.image;
+    const auto t_pass = Clock::now();
+    const uint64_t npixel = d.in.npixel, nvoxel = d.in.nvoxel;
+    const uint64_t nb = (uint64_t)hc.nb(), nc = (uint64_t)hc.K + 1, ncam = (uint64_t)hc.ncam(), T = frames.size();
+    const uint64_t per_frame = nb * nc, nvirt = T * per_frame, per_col = ncam * kHoldoutSums;
+    const int fallback = holdout_fallback(hc.betas.data(), (int)nb, cfg.beta_laplace);
+    FitProjector fp(d, sh);
+    const std::vector<double> ell = fp.ray_lengths();
+    std::unique_ptr<CompositeImage> full;
+    DeviceArray<double> dF, dg, dell, dsums;
+    DeviceArray<int32_t> dfold, dheld;
+    DeviceArray<int64_t> dcam;
+    struct Events {  // the scoring kernel's time (--profile)
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        ~Events() {
+            if (e0) (void)hipEventDestroy(e0);
+            if (e1) (void)hipEventDestroy(e1);
+        }
+    } ev;
+    if (d.rank == 0) {
+        full = all_pixel_image(d);
+        dF.resize((size_t)fp.group * npixel), dg.resize(npixel), dell.resize(npixel), dfold.resize(npixel);
+        dheld.resize((size_t)fp.group), dcam.resize(ncam + 1), dsums.resize((size_t)fp.group * per_col);
+        hip_ok(hipMemcpy(dell.get(), ell.data(), npixel * sizeof(double), hipMemcpyHostToDevice), "H2D ray lengths");
+        hip_ok(hipMemcpy(dfold.get(), hc.folds.data(), npixel * sizeof(int32_t), hipMemcpyHostToDevice), "H2D folds");
+        hip_ok(hipMemcpy(dcam.get(), hc.cam_start.data(), (ncam + 1) * sizeof(int64_t), hipMemcpyHostToDevice),
+               "H2D cameras");
+        hip_ok(hipEventCreate(&ev.e0), "hipEventCreate");
+        hip_ok(hipEventCreate(&ev.e1), "hipEventCreate");
+    }
+    std::vector<double> sums(d.rank == 0 ? nvirt * per_col : 0), x(nvoxel), g;
+    std::vector<int32_t> held((size_t)fp.group);
+    uint64_t g_frame = T, decided = 0;  // g: the measured frame g_frame (on the device too); frames [0, decided) are scored
+    double scoring_ms = 0.0;
+    const uint64_t groups = fp.for_groups(
+        nvirt, [&](uint64_t j0, int n, double* X) { hc.file->read_columns(j0, n, X); },
+        [&](uint64_t j0, int n, const double* F) {
+            hip_ok(hipMemcpy(dF.get(), F, (size_t)n * npixel * sizeof(double), hipMemcpyHostToDevice), "H2D images");
+            for (int a = 0; a < n;) {  // the columns [a, b) of the group belong to one composite frame
+                const uint64_t k = (j0 + a) / per_frame;
+                int b = a;
+                while (b < n && (j0 + b) / per_frame == k) ++b;
+                if (k != g_frame) {
+                    g = full->frame(frames[k]), g_frame = k;
+                    hip_ok(hipMemcpy(dg.get(), g.data(), npixel * sizeof(double), hipMemcpyHostToDevice), "H2D frame");
+                }
+                for (int j = a; j < b; ++j) held[j - a] = (int32_t)((j0 + j) % nc) - 1;
+                hip_ok(hipMemcpy(dheld.get(), held.data(), (size_t)(b - a) * sizeof(int32_t), hipMemcpyHostToDevice),
+                       "H2D held folds");
+                hip_ok(hipEventRecord(ev.e0, nullptr), "hipEventRecord");
+                launch_holdout64(dF.get() + (size_t)a * npixel, (int64_t)npixel, b - a, dg.get(), dell.get(),
+                                 cfg.ray_length_threshold, dfold.get(), dheld.get(), dcam.get(), (int)ncam, dsums.get(),
+                                 nullptr);
+                hip_ok(hipEventRecord(ev.e1, nullptr), "hipEventRecord");
+                hip_ok(hipMemcpy(sums.data() + (j0 + a) * per_col, dsums.get(), (size_t)(b - a) * per_col * sizeof(double),
+                                 hipMemcpyDeviceToHost), "D2H hold-out sums");
+                float ms = 0.f;
+                hip_ok(hipEventElapsedTime(&ms, ev.e0, ev.e1), "hipEventElapsedTime");
+                scoring_ms += ms;
+                a = b;
+            }
+            for (; (decided + 1) * per_frame <= j0 + n; ++decided) {
+                const uint64_t k = decided, cur = frames[k];
+                const HoldoutScores sc = holdout_scores(sums.data() + k * per_frame * per_col,
+                                                        hc.ok.data() + k * per_frame, (int)nb, hc.K, (int)ncam, fallback);
+                hc.file->write_frame(k, sums.data() + k * per_frame * per_col, sc);
+                const uint64_t js = (k * nb + (uint64_t)sc.selected) * nc;
+                hc.file->read_columns(js, 1, x.data());  // the stored row itself: /solution/value[k] is its bits
+                hc.file->close();                        // the solution writer opens the file itself
+                d.writer->add(x, hc.status[js], image.frame_time(cur), image.camera_frame_time(cur), hc.iterations[js]);
+            }
+        });
+    d.host->barrier();
+    if (d.rank == 0) {
+        const double ms = ms_since(t_pass);
+        std::cout << "Hold-out of " << T << " frame(s) x " << nb << " weights x " << hc.K << " folds in: " << ms << " ms"
+                  << std::endl;
+        if (d.profile.is_open())
+            write_holdout_line(d.profile, {cfg.holdout_cameras ? "cameras" : "pixels", hc.K, cfg.holdout_seed, nb, T,
+                                           nvirt, groups, scoring_ms, ms});
+    }
 }
 
 }  // namespace sart

@@ -91,6 +91,12 @@ void write_phantom_line(std::ostream& os, const PhantomLine& p) {
         "projection_kernel_ms", p.projection_kernel_ms)("scoring_kernel_ms", p.scoring_kernel_ms).end();
 }
 
+void write_holdout_line(std::ostream& os, const HoldoutLine& h) {
+    JsonLine j(os);
+    j("holdout", true)("mode", h.mode)("folds", h.folds)("seed", h.seed)("betas", h.betas)("frames", h.frames)(
+        "columns", h.columns)("groups", h.groups)("scoring_kernel_ms", h.scoring_kernel_ms)("ms", h.ms).end();
+}
+
 void write_fit_line(std::ostream& os, uint64_t frames, uint64_t groups, double ms, const char* storage,
                     const char* format, int ranks) {
     JsonLine j(os);

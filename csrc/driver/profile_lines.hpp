@@ -103,6 +103,16 @@ struct PhantomLine {
     double projection_kernel_ms, scoring_kernel_ms;
 };
 void write_phantom_line(std::ostream& os, const PhantomLine& p);
+// --holdout: the run's shape, the projection groups of the hold-out pass, the scoring kernel's total time (device events
+// around rank 0's launches) and the pass's wall time on rank 0
+struct HoldoutLine {
+    const char* mode;
+    int folds;
+    uint64_t seed;
+    uint64_t betas, frames, columns, groups;
+    double scoring_kernel_ms, ms;
+};
+void write_holdout_line(std::ostream& os, const HoldoutLine& h);
 void write_fit_line(std::ostream& os, uint64_t frames, uint64_t groups, double ms, const char* storage,
                     const char* format, int ranks);
 

@@ -22,9 +22,11 @@
 // the output's /beta_scan group, its corner's solution into /solution), --replicas N (every frame and N noisy replicas
 // of it as columns of the multi-frame engine; per-voxel mean and spread into the output's /uncertainty group),
 // --phantom FILE (the frames solved are the fp64 projections of known emissivities through the shard; every column
-// scored against its truth into the output's /phantom group).
+// scored against its truth into the output's /phantom group), --holdout K|cameras (every frame as measured and with
+// each fold of its pixels -- or each camera -- excluded, as columns of the multi-frame engine; the prediction errors of
+// the held-out pixels into the output's /holdout group, the best weight's unmasked column into /solution).
 // This file: main()'s sequence up to the runs it starts (driver.hpp). The frame loops: series_runs.cpp (frame by frame,
-// --batch_frames) and column_runs.cpp (--beta_scan, --replicas, --phantom), on the series skeleton of driver.hpp with the order
+// --batch_frames) and column_runs.cpp (--beta_scan, --replicas, --phantom, --holdout), on the series skeleton of driver.hpp with the order
 // rules of series_order.hpp and the frame reader of frame_readahead.hpp; the passes after the frames: fit_pass.cpp. The
 // shard and its loaders: shard_load.{hpp,cpp}; the --profile lines: profile_lines.
 #include <sys/prctl.h>
@@ -65,7 +67,8 @@ Solvers build_solvers(const Driver& d, Shard& sh, const SolverParams& params, co
         // batch width 16, 32, 64 or 128 (rounded up; 128: bf16 storage and f16-pair split-A); sparse shards: fp32 SpMM
         // projections of the CSR / CSC; bf16 / f16 shards: MFMA projections
         base.mf_frames = cfg.batch_frames;
-        base.mf_frame_beta = !cfg.beta_scan.empty();  // the scan brings a weight per column: keep the Laplacian
+        // the scan (and a hold-out ladder) brings a weight per column: keep the Laplacian
+        base.mf_frame_beta = !cfg.beta_scan.empty() || !cfg.holdout_betas.empty();
         s.mf = make_engine<MultiFrameEngine>(sh, d.device, d.dcomm.get(), base, lap);
         // a cold time series' first frame: the single-frame engine, built with the set-up (before the frame loop's
         // clock, like the frame-by-frame engine); dropped after that frame (SART_MF_LEAD_ENGINE=0: none)
@@ -163,11 +166,11 @@ void open_output(Driver& d, Resume& r) {
                 r.warm = stored.last_solution;
             }
         }
-        // --beta_scan, --replicas, --phantom: the run creates the file with its own group; /solution is added to it
+        // --beta_scan, --replicas, --phantom, --holdout: the run creates the file with its own group; /solution is added to it
         d.writer = std::make_unique<SolutionWriter>(cfg.output_file, d.in.camera_names, d.in.nvoxel,
                                                     (uint64_t)cfg.max_cached_solutions, r.appended,
                                                     !cfg.beta_scan.empty() || cfg.replicas > 0 ||
-                                                        !cfg.phantom_file.empty());
+                                                        !cfg.phantom_file.empty() || cfg.holdout_on());
         r.voxelgrid.read(d.in.rtm_files.begin()->second, "rtm/voxel_map");
         for (const auto& m : r.voxelgrid.warnings) std::cerr << "warning: " << m << std::endl;
     }
@@ -191,6 +194,37 @@ SolverParams solver_params(const Config& cfg) {
     return params;
 }
 
+// --holdout: the folds of all pixels and the cameras' pixel ranges (every rank: the inputs' metadata alone); rank 0: the
+// output file created with its /holdout group
+HoldoutColumns holdout_columns(const Driver& d, size_t T) {
+    const Config& cfg = d.cfg;
+    const InputSet& in = d.in;
+    HoldoutColumns hc;
+    std::vector<int64_t> camera_pixels;
+    hc.cam_start.push_back(0);
+    for (const auto& cam : in.camera_names) {
+        const auto& mask = in.frame_masks.at(cam);
+        camera_pixels.push_back((int64_t)std::count_if(mask.begin(), mask.end(), [](int32_t v) { return v != 0; }));
+        hc.cam_start.push_back(hc.cam_start.back() + camera_pixels.back());
+    }
+    if ((uint64_t)hc.cam_start.back() != in.npixel) throw std::runtime_error("the cameras' masks do not add up to the pixels");
+    hc.K = cfg.holdout_cameras ? (int)camera_pixels.size() : cfg.holdout;
+    hc.betas = cfg.holdout_betas.empty() ? std::vector<double>{cfg.beta_laplace} : cfg.holdout_betas;
+    hc.folds.resize(in.npixel);
+    if (cfg.holdout_cameras)
+        holdout_camera_folds(camera_pixels.data(), (int)camera_pixels.size(), 0, in.npixel, hc.folds.data());
+    else
+        holdout_pixel_folds(cfg.holdout_seed, hc.K, 0, in.npixel, hc.folds.data());
+    if (d.rank == 0) {
+        const size_t nvirt = T * hc.betas.size() * (size_t)(hc.K + 1);
+        hc.file = std::make_unique<HoldoutWriter>(cfg.output_file, T, hc.betas.size(), (uint64_t)hc.K, camera_pixels.size(),
+                                                  in.nvoxel, cfg.holdout_cameras, hc.folds.data(), in.npixel,
+                                                  cfg.holdout_seed, hc.betas.data());
+        hc.status.resize(nvirt), hc.iterations.resize(nvirt), hc.ok.resize(nvirt);
+    }
+    return hc;
+}
+
 // Everything after the communicators exist: an exception here aborts them (main)
 void run(Driver& d) {
     const Config& cfg = d.cfg;
@@ -200,6 +234,11 @@ void run(Driver& d) {
     d.cols = d.gpu && cfg.partition_voxels;
     if (cfg.replicas > 0 && in.npixel >= (uint64_t)1 << 32)  // the noise counter takes the pixel index as 32 bits
         throw Error("Argument replicas applies to fewer than 2^32 pixels, " + std::to_string(in.npixel) + " given.");
+    if (cfg.holdout_on() && in.npixel >= (uint64_t)1 << 32)  // the fold counter takes the pixel index as 32 bits
+        throw Error("Argument holdout applies to fewer than 2^32 pixels, " + std::to_string(in.npixel) + " given.");
+    if (cfg.holdout_cameras && in.camera_names.size() < 2)
+        throw Error("Argument holdout cameras needs at least two cameras, " + std::to_string(in.camera_names.size()) +
+                    " given.");
     d.vblk = d.cols ? block_partition(in.nvoxel, size, rank) : Block{0, in.nvoxel};
     d.blk = d.cols ? Block{0, in.npixel} : block_partition(in.npixel, size, rank);  // reference main.cpp:67-68
     if (d.blk.size == 0 || d.vblk.size == 0)
@@ -265,6 +304,11 @@ void run(Driver& d) {
         run_scan_series(d, solvers, frames, sc);
         solvers.reset();  // the engine's device buffers, before the pass allocates its own
         run_scan_pass(d, shard, lap, frames, sc);
+    } else if (cfg.holdout_on()) {
+        HoldoutColumns hc = holdout_columns(d, frames.size());
+        run_holdout_series(d, solvers, frames, hc);
+        solvers.reset();  // the engine's device buffers, before the pass allocates its own
+        run_holdout_pass(d, shard, frames, hc);
     } else if (cfg.replicas > 0)
         run_replica_series(d, solvers, frames);
     else if (batched)

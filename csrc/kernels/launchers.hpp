@@ -173,6 +173,18 @@ constexpr int kPhantomSums = 10;
 int64_t phantom64_scratch_elems(int64_t nvoxel);
 void launch_phantom64(const double* X, int64_t ldx, int64_t nvoxel, int nv, const double* t, double* sums_out,
                       double* scratch, hipStream_t stream);
+// holdout64.hip: the hold-out sums of n fp64 fitted images F [n][ldf] against one frame g over the pixels of ncam
+// cameras (camera m: the pixels cam_start[m] .. cam_start[m + 1] - 1; all device arrays). A pixel counts when g >= 0
+// and ell > threshold (a NaN in either: it does not); column j holds out the counted pixels with fold == held[j]
+// (held[j] = -1: none). sums [n][ncam][kHoldoutSums]: sum (g - f)^2, sum g^2 and the count over the held-out pixels,
+// then the same three over the others. Plain fp64 (no contraction): thread t of a block of 256 takes the pixels
+// cam_start[m] + t, + 256, ... in order, then a fixed tree over the 256 threads in LDS; no atomics, no scratch: a value
+// depends on its column, its camera range and the inputs alone. Nothing at or beyond cam_start[ncam] is read.
+// 1 <= n <= 65535, ncam >= 1, ldf >= cam_start[ncam] (the caller's to keep).
+constexpr int kHoldoutSums = 6;
+void launch_holdout64(const double* F, int64_t ldf, int n, const double* g, const double* ell, double threshold,
+                      const int32_t* fold, const int32_t* held, const int64_t* cam_start, int ncam, double* sums,
+                      hipStream_t stream);
 // sart_update.hip
 void launch_prep_rows(const double* g, int64_t nrows, int64_t nrows_pad, double inv_s, const float* ray_length,
                       float len_thres, float* ghat, float* arow, float* gpos, float* wo, hipStream_t stream);

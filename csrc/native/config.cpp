@@ -57,8 +57,8 @@ std::string fmt(double v) {
 }
 
 // "B0,B1,...": 3 .. 64 finite values >= 0 in strictly increasing order; anything else is one error, with the text given
-std::vector<double> to_beta_scan(const std::string& text) {
-    const Error bad("Argument beta_scan must list 3 to 64 increasing values >= 0, " + text + " given.");
+std::vector<double> to_beta_scan(const std::string& text, const std::string& name = "beta_scan") {
+    const Error bad("Argument " + name + " must list 3 to 64 increasing values >= 0, " + text + " given.");
     std::vector<double> out;
     size_t pos = 0;
     while (true) {
@@ -176,14 +176,30 @@ std::string usage() {
            "                              gets N noisy replicas. Implies --no_guess and --batch_frames >= 16. Not with\n"
            "                              --use_cpu, --batch_frames 1, --fp64, --partition_voxels, --resume, --fit,\n"
            "                              --fit_only or --beta_scan.\n"
+           "  --holdout K|cameras         Cross-validation: solve every frame as measured and with each of K (2 to 32)\n"
+           "                              pseudo-random folds of its pixels excluded -- or, with 'cameras', with each\n"
+           "                              camera excluded in turn (at least two cameras) -- in one batched run: every\n"
+           "                              masked frame is a column of the multi-frame engine. The solutions are projected\n"
+           "                              in fp64 and the prediction errors of the held-out pixels (in all, per camera)\n"
+           "                              go to the output file's /holdout group with every column; the unmasked column\n"
+           "                              of the weight with the smallest error goes to /solution. Implies --no_guess and\n"
+           "                              --batch_frames >= 16. Not with --use_cpu, --fp64, --partition_voxels, --resume,\n"
+           "                              --fit, --fit_only, --beta_scan, --replicas or --phantom.\n"
+           "  --holdout_seed S            With --holdout K: 64-bit seed of the pixel folds (a pixel's fold depends on the\n"
+           "                              seed and the pixel alone). [default: 0]\n"
+           "  --holdout_betas B0,B1,...   With --holdout: run the folds at each of these Laplacian weights (3 to 64\n"
+           "                              increasing values >= 0; needs -l) and select the weight by its cross-validation\n"
+           "                              error; -b names the fallback (the nearest entry). Without it every column runs\n"
+           "                              at -b.\n"
            "  --profile FILE              Write per-frame timing/iteration telemetry as JSON lines.\n";
 }
 
 Config parse_arguments(const std::vector<std::string>& argv) {
     Config c;
     bool semantics_given = false, scan_given = false, replicas_given = false, noise_given = false;
-    bool batch_given = false, phantom_given = false;
-    std::string scan_text;
+    bool batch_given = false, phantom_given = false, holdout_given = false, holdout_seed_given = false;
+    bool holdout_betas_given = false;
+    std::string scan_text, holdout_text, holdout_betas_text;
     using Setter = std::function<void(const std::string&, const std::string&)>;
     std::map<std::string, Setter> valued = {
         {"--output_file", [&](const std::string& v, const std::string&) { c.output_file = v; }},
@@ -210,6 +226,9 @@ Config parse_arguments(const std::vector<std::string>& argv) {
         {"--noise_rel", [&](const std::string& v, const std::string& o) { c.noise_rel = to_double(v, o); noise_given = true; }},
         {"--noise_seed", [&](const std::string& v, const std::string& o) { c.noise_seed = to_u64(v, o); noise_given = true; }},
         {"--phantom", [&](const std::string& v, const std::string&) { c.phantom_file = v; phantom_given = true; }},
+        {"--holdout", [&](const std::string& v, const std::string&) { holdout_text = v; holdout_given = true; }},
+        {"--holdout_seed", [&](const std::string& v, const std::string& o) { c.holdout_seed = to_u64(v, o); holdout_seed_given = true; }},
+        {"--holdout_betas", [&](const std::string& v, const std::string&) { holdout_betas_text = v; holdout_betas_given = true; }},
     };
     std::map<std::string, bool*> flags = {
         {"--logarithmic", &c.logarithmic}, {"--no_guess", &c.no_guess},   {"--use_cpu", &c.use_cpu},
@@ -341,6 +360,32 @@ Config parse_arguments(const std::vector<std::string>& argv) {
             throw Error("Argument phantom writes its own output: it cannot be combined with resume, fit, fit_only or "
                         "beta_scan.");
         // every phantom (and every replica of it) is a cold column of the batch engine, as a weight of the scan is
+        if (c.batch_frames == 1) c.batch_frames = 16;
+        c.no_guess = true;
+    }
+    if ((holdout_seed_given || holdout_betas_given) && !holdout_given)
+        throw Error("Arguments holdout_seed and holdout_betas need holdout.");
+    if (holdout_given) {
+        if (trim(holdout_text) == "cameras") {
+            c.holdout_cameras = true;
+        } else {
+            c.holdout = to_int(holdout_text, "--holdout");
+            if (c.holdout < 2 || c.holdout > 32)
+                throw Error("Argument holdout must be cameras or a number of folds within 2 .. 32, " +
+                            std::to_string(c.holdout) + " given.");
+        }
+        if (holdout_seed_given && c.holdout_cameras)
+            throw Error("Argument holdout_seed applies to pixel folds: it cannot be combined with holdout cameras.");
+        if (holdout_betas_given) {
+            c.holdout_betas = to_beta_scan(holdout_betas_text, "holdout_betas");
+            if (c.laplacian_file.empty()) throw Error("Argument holdout_betas needs a laplacian_file.");
+        }
+        if (c.use_cpu || c.fp64 || c.partition_voxels)
+            throw Error("Argument holdout applies to the batched GPU solver with pixel-row shards only.");
+        if (c.resume || c.fit || c.fit_only || scan_given || replicas_given || phantom_given)
+            throw Error("Argument holdout writes its own output: it cannot be combined with resume, fit, fit_only, "
+                        "beta_scan, replicas or phantom.");
+        // every masked frame is a cold column of the batch engine, as a weight of the scan is
         if (c.batch_frames == 1) c.batch_frames = 16;
         c.no_guess = true;
     }

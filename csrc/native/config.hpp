@@ -4,7 +4,7 @@
 // arguments.cpp:82-251, arguments.hpp:14-33), with an in-tree parser instead of p-ranav/argparse.
 // Extensions (not in the reference) are marked: --resume, --batch_frames, --two_pass, --partition_voxels,
 // --profile, --fp64, --fp64_semantics, --fit, --fit_only, --beta_scan, --replicas (with --noise_abs, --noise_shot,
-// --noise_rel, --noise_seed, --replicas_keep), --phantom.
+// --noise_rel, --noise_seed, --replicas_keep), --phantom, --holdout (with --holdout_seed, --holdout_betas).
 #pragma once
 
 #include <array>
@@ -65,6 +65,16 @@ struct Config {
     // /phantom/value through the RTM as stored (with `replicas`: and noisy replicas of them), scored against their truth
     // into the output's /phantom group, column 0 into /solution. Implies batch_frames >= 16 and no_guess. Empty: off
     std::string phantom_file;
+    // Hold-out cross-validation: every frame as measured and with each of K folds of its pixels excluded, at every
+    // weight of holdout_betas (none: at beta_laplace), in one batched run; the prediction errors of the held-out pixels
+    // into the output's /holdout group, the best weight's unmasked column into /solution. holdout: K (2 .. 32) pseudo-
+    // random pixel folds keyed by holdout_seed, or with holdout_cameras one fold per camera (K = the number of cameras,
+    // known with the inputs). Implies batch_frames >= 16 and no_guess. 0 and false: off
+    int holdout = 0;
+    bool holdout_cameras = false;
+    uint64_t holdout_seed = 0;
+    std::vector<double> holdout_betas;
+    bool holdout_on() const { return holdout > 0 || holdout_cameras; }
     std::string profile_file;  // JSON timing/telemetry sidecar
     bool help = false;
 };
